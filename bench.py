@@ -21,7 +21,19 @@ fp32 product as P 16-bit piece products, the dense bf16/fp16 MFMA peak / P
 (fp16x2, the default: P = 3, 2500 / 3 = 833.3 TF of fp32-equivalent work;
 bf16x3: P = 6, 416.7 TF).
 
-CPU baseline: the oracle (a torch-CPU restatement of the reference path,
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+folds, writes the last fold's images if `--dump-outputs DIR` is given and
+prints the result line; the roofline fields come from the events of the timed
+region itself. `--full` adds what takes a run of its own: the CPU baseline.
+
+`--dump-outputs DIR`: after the timed folds rank 0 writes what the last timed
+fold returned (the images of all ranks, in rank order) as
+DIR/samples.npy, float32. The weights and the per-rank noise seeds are fixed,
+so with the same arguments two builds sample from identical inputs and their
+files compare image for image. More than DUMP_LIMIT_BYTES: a fixed, seeded
+subset of the images, in ascending order.
+
+CPU baseline (`--full`): the oracle (a torch-CPU restatement of the reference path,
 bit-equal to it at equal thread count) timed on all usable host cores, rank 0 /
 N=1 only: one warm-up step and 8 timed denoising steps of the same B=256 fold
 (about 10 s of CPU work: the 3-step sample of round 3 scattered 0.79-0.88 img/s
@@ -49,6 +61,7 @@ FP32_PEAK_TFLOPS = 157.3   # MI355X dense fp32 (MFMA f32 = vector rate), MI355X_
 BF16_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 MFMA (no sparsity), MI355X_MICROARCH.md
 SPLIT_PRODUCTS = {2: 3, 3: 6}  # conv_patch3_kernel<..., NP>: fp16x2 issues 3, bf16x3 6 piece products per product
 HBM_PEAK_GBS = 8000.0
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # --dump-outputs: all files together stay under 64 MB
 PROFILE_EVERY = 10   # per-launch events cost ~5 % when on every launch; 1 forward in 10 is observed
 
 
@@ -61,12 +74,35 @@ def parse():
                     help='; '.join(f'{k}: {v}' for k, v in sorted(WORKLOADS.items())))
     ap.add_argument('--batch', type=int, default=None, help='images per GPU per fold (default: the workload\'s)')
     ap.add_argument('--respace-steps', type=int, default=None, help='denoising steps (default: the workload\'s)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also what takes a run of its own after the timed folds: the CPU baseline (N=1)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the images of the last timed fold to DIR/samples.npy (float32, rank 0)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-batch', type=int, default=256, help='batch of the timed CPU denoising step')
     ap.add_argument('--profile-json', default=None, help='write the per-op profile here (rank 0)')
     ap.add_argument('--no-profile', action='store_true',
                     help='no per-launch HIP events in the timed region (roofline fields then null)')
     return ap.parse_args()
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write each tensor of `arrays` (name -> tensor, first dimension = images) as dirname/<name>.npy in float32.
+    All files together hold at most `limit` bytes: a larger tensor is cut to a subset of its images drawn with a
+    fixed seed (the same subset on every run), kept in ascending order. Returns name -> kept image indices or None."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = limit // max(1, len(arrays))
+    kept = {}
+    for name, t in arrays.items():
+        a = t.detach().to('cpu', torch.float32).contiguous().numpy()
+        kept[name] = None
+        if a.nbytes > budget:
+            rows = max(1, budget // max(1, a[0].nbytes))
+            idx = np.sort(np.random.default_rng(2022).choice(a.shape[0], size=rows, replace=False))
+            a, kept[name] = a[idx], idx.tolist()
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+    return kept
 
 
 def pmc_traffic(label, workload='c3', build=None, launches_per_forward=None, root=ROOT):
@@ -532,8 +568,9 @@ def main():
     barrier()
     sync()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        fold()
+        last = fold()   # kept for --dump-outputs
     sync()
     barrier()
     elapsed = time.perf_counter() - t0
@@ -620,7 +657,7 @@ def main():
         if args.workload != 'c3':
             line['config']['bench_workload'] = args.workload
         line['cpu_baseline'] = None
-        if world == 1 and not args.no_cpu_baseline and wl['sd_cpu'] is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and wl['sd_cpu'] is not None:
             if args.workload in ('c2', 'c3'):
                 line['cpu_baseline'] = cpu_baseline(wl['sd_cpu'], args.cpu_batch, wl['denoise_steps'])
             else:
@@ -632,6 +669,8 @@ def main():
         if args.profile_json:
             with open(args.profile_json, 'w') as f:
                 json.dump(dict(families=fam, ops=prof), f, indent=1)
+        if args.dump_outputs and last is not None:
+            dump_outputs(args.dump_outputs, dict(samples=last))
         print(json.dumps(line), flush=True)
     if comm is not None:
         comm.close()

@@ -15,7 +15,7 @@ for w in ${WORKLOADS:-c3 c2 c4 c5}; do
   mkdir -p gpurun_out/profiles_out && cp profiles/${tag}_* gpurun_out/profiles_out/
   rm -rf gpurun_out/prof_${tag} gpurun_out/pmc_fetch_${tag} gpurun_out/pmc_write_${tag}
   echo "== bench $w"; date
-  extra=""; [ "$w" != c3 ] && extra="--steps 1 --warmup 1"
+  extra="--full"; [ "$w" != c3 ] && extra="--full --steps 1 --warmup 1"   # --full: the line carries the CPU baseline
   timeout -k 10 900 python3 bench.py --workload $w $extra > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err \
     || { tail -20 gpurun_out/${tag}_bench.err; exit 1; }
   cat gpurun_out/${tag}_bench.json

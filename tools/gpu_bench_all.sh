@@ -12,6 +12,6 @@ step() {  # name, timeout, command...
   if [ $rc -ne 0 ]; then echo "stopping after $name (rc=$rc)"; exit $rc; fi
 }
 for w in ${WORKLOADS:-c5 c2}; do
-  step bench_$w ${WL_TIMEOUT:-600} python -u bench.py --workload $w --steps 1 --warmup 0 \
+  step bench_$w ${WL_TIMEOUT:-600} python -u bench.py --full --workload $w --steps 1 --warmup 0 \
     --profile-json gpurun_out/bench_${w}_profile.json $BENCH_ARGS
 done
