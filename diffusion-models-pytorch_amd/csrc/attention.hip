@@ -968,3 +968,28 @@ int attn_fused(const AttnArgs& args, hipStream_t st) {
 }
 
 }  // namespace dm
+
+/* Test hook (tests/test_gpu_attention_ops.py): one attn_fused() launch on the caller's device buffers -- the planes
+ * pq / pk / pv ([B][heads][2][L][Dh], v^T [B][heads][2][Dh][L]) or, with the planes null, fp32 qkv rows -- dispatched
+ * to attn_flash, attn_presplit_kernel or attn_fused_kernel exactly as the plans' calls are; out fp32 rows of pitch
+ * ldo, or o_split (flash only) the pre-split A image of pitch o_ld. No fuse_proj. Synchronous; allocates nothing. */
+extern "C" int dm_debug_attention(const void* pq, const void* pk, const void* pv, const float* qkv, int ld, int q0,
+                                  int k0, int v0, int hs, int B, int heads, int L, int Dh, float alpha, float b_scale,
+                                  int ea, int eb, int ep, int ev, float* out, int ldo, void* o_split, int o_split_ea,
+                                  int o_ld, int* range_flag, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (B <= 0 || heads <= 0 || L <= 0 || Dh <= 0) { set_error("bad attention shape"); return DM_ERR_ARG; }
+  AttnArgs a{};
+  a.pq = (const _Float16*)pq; a.pk = (const _Float16*)pk; a.pv = (const _Float16*)pv;
+  a.qkv = qkv; a.ld = ld; a.q0 = q0; a.k0 = k0; a.v0 = v0; a.hs = hs;
+  a.B = B; a.heads = heads; a.L = L; a.Dh = Dh; a.alpha = alpha; a.b_scale = b_scale;
+  a.ea = ea; a.eb = eb; a.ep = ep; a.ev = ev;
+  a.out = out; a.ldo = ldo;
+  a.o_split = (_Float16*)o_split; a.o_split_ea = o_split_ea; a.o_ld = o_ld;
+  a.range_flag = range_flag;
+  const int rc = attn_fused(a, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}

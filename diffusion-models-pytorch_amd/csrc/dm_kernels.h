@@ -431,7 +431,7 @@ int attn_fold(const float* wqkv, const float* bqkv, const float* wproj, const fl
 int attn_block(const AttnBlockArgs& a, hipStream_t st);
 // wgp = wg with its columns permuted within 32-groups as attn_block variant 3 reads its projection operand
 int attn_perm_cols(const float* wg, float* wgp, int C, hipStream_t st);
-// Flash attention (attention.hip attn_flash_kernel) on pre-split planes for L % 64 == 0, head dims 8 .. 80:
+// Flash attention (attention.hip attn_flash_kernel) on pre-split planes for L % 64 == 0, head dims 32, 64, 72, 80:
 // ADM's L = 1024 / 64 blocks, DiT's 72-wide heads. attn_fused dispatches there for shapes it does not take.
 bool attn_flash_ok(int L, int Dh);
 int attn_flash(const AttnArgs& a, hipStream_t st);
