@@ -2,6 +2,10 @@
 //   * LayerNorm row statistics for the fused LN + adaLN-modulate GEMM prologue
 //     (DiTBlock norm1 / norm2, FinalLayer norm_final: eps 1e-6, no affine);
 //   * patchify (PatchEmbed's Conv2d k = s = p as a GEMM input) and unpatchify.
+// row_stats_split dispatches on the row width: D <= 1280 to row_stats_split_reg_kernel, wider rows to the
+// streaming row_stats_split_kernel (no model shipped here has D > 1280; tests/test_gpu_token_ops.py runs it at
+// D = 1344 and 2048 through dm_debug_row_stats, below, and finds its image bit-identical to row_stats +
+// linear_presplit_a). Every kernel of this file has operator tests there.
 #include "dm_common.h"
 #include "dm_kernels.h"
 #include "split16.h"
@@ -241,3 +245,36 @@ int unpatchify(const float* x, int B, int C, int H, int W, int p, float* out, hi
 }
 
 }  // namespace dm
+
+/* Test hooks (tests/test_gpu_token_ops.py): one launch each on the caller's device buffers; synchronous, allocate
+ * nothing. dm_debug_row_stats: out_img null -> row_stats, else row_stats_split (row_stats_split_reg_kernel for
+ * D <= 1280, the streaming row_stats_split_kernel beyond). dm_debug_patchify: inverse 0 patchify (x NCHW [B][C][S][S]
+ * -> rows), 1 unpatchify (rows -> NCHW). */
+extern "C" int dm_debug_row_stats(const float* x, long rows, int D, float eps, void* stats, const float* ln_shift,
+                                  const float* ln_scale, int ln_pitch, int ln_rows, int split_ea, void* out_img,
+                                  int* range_flag, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !stats || rows <= 0 || D <= 0) { set_error("bad row_stats arguments"); return DM_ERR_ARG; }
+  int rc;
+  if (!out_img) {
+    rc = row_stats(x, rows, D, eps, (float2*)stats, st);
+  } else {
+    if (!ln_shift || !ln_scale || ln_pitch < D) { set_error("row_stats_split needs the modulation tables"); return DM_ERR_ARG; }
+    rc = row_stats_split(x, rows, D, eps, (float2*)stats, ln_shift, ln_scale, ln_pitch, ln_rows, split_ea,
+                         (_Float16*)out_img, range_flag, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+extern "C" int dm_debug_patchify(const float* x, int B, int C, int S, int p, float* out, int inverse, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !out || B <= 0 || C <= 0 || S <= 0 || p <= 0) { set_error("bad patchify arguments"); return DM_ERR_ARG; }
+  const int rc = inverse ? unpatchify(x, B, C, S, S, p, out, st) : patchify(x, B, C, S, S, p, out, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}

@@ -287,7 +287,11 @@ int embed_add_silu(const float* temb, const int64_t* y, const float* table, int 
                    hipStream_t st, int null_row = -1);
 // LayerNorm statistics (no affine): stats[r] = (mean, 1 / sqrt(var + eps)) of each D-wide row
 int row_stats(const float* x, long rows, int D, float eps, float2* stats, hipStream_t st);
-// row_stats + LayerNorm + adaLN modulate + fp16x2 split of each row: the pre-split A image (GemmArgs::as)
+// row_stats + LayerNorm + adaLN modulate + fp16x2 split of each row: the pre-split A image (GemmArgs::as).
+// D <= 1280 runs row_stats_split_reg_kernel (the row in registers), wider rows the streaming
+// row_stats_split_kernel. Operator tests of both forms, of row_stats, patchify / unpatchify and embed_add_silu:
+// tests/test_gpu_token_ops.py through dm_debug_row_stats / dm_debug_patchify / dm_debug_embed_add_silu; of every
+// linear_k32 / gemm.hip form of the token GEMMs through dm_debug_token_gemm (linear_k32.hip).
 int row_stats_split(const float* x, long rows, int D, float eps, float2* stats, const float* ln_shift,
                     const float* ln_scale, int ln_pitch, int ln_rows, int split_ea, _Float16* out, int* range_flag,
                     hipStream_t st);

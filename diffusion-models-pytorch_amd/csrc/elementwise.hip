@@ -821,3 +821,16 @@ int repack_conv(const float* w, int Cout, int Cin, int taps, float* out, int ldw
 }
 
 }  // namespace dm
+
+/* Test hook (tests/test_gpu_token_ops.py): one embed_add_silu launch on the caller's device buffers (y null: no
+ * labels; null_row < 0: no class term for rows without a label). Synchronous; allocates nothing. */
+extern "C" int dm_debug_embed_add_silu(const float* temb, const int64_t* y, const float* table, int B, int D,
+                                       float* out, int null_row, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!temb || !table || !out || B <= 0 || D <= 0) { set_error("bad embed_add_silu arguments"); return DM_ERR_ARG; }
+  const int rc = embed_add_silu(temb, y, table, B, D, out, st, null_row);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}

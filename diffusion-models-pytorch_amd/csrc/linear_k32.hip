@@ -836,3 +836,134 @@ extern "C" int dm_debug_linear_k32(const float* A, int lda, const float* W, cons
   if (skc) (void)hipFree(skc);
   return rc;
 }
+
+/* Test hook (tests/test_gpu_token_ops.py): one token GEMM through gemm_batched on the caller's device buffers, every
+ * GemmArgs field of the DiT forms settable. path 0: linear_k32 on weights W [N][K] the hook splits (its only
+ * temporaries, with the split-K workspace when sk = 1); 1: gemm.hip fp16x2 (split_eb from split_weight_exponent);
+ * 2: gemm.hip fp32 (the range fallback's arithmetic). a_form 0: prologue and split in the GEMM; 1: linear_presplit_a
+ * into the caller's `as`, then (path 0) the GEMM on that image without a prologue -- gemm.hip has no pre-split
+ * input: paths 1 / 2 write the image and run the GEMM as a_form 0; 2 (path 0): the caller's `as` as given.
+ * A descriptor linear_k32_ok refuses (path 0), or a gemm.hip path asked for a linear_k32-only output, returns
+ * DM_ERR_UNSUPPORTED and launches nothing. Synchronous. */
+struct dm_debug_gemm_desc {
+  int M, N, K;
+  int path, a_form, sk;
+  const float* A;
+  int lda;
+  const float* W;
+  float* C;
+  int ldc;
+  const float* bias;
+  const float* res;
+  int ld_res, res_mod;
+  const float* gate;
+  int gate_pitch, gate_rows;
+  int act;
+  float alpha;
+  const float* pro_scale;
+  const float* pro_shift;
+  int pro_rows;
+  const void* ln_stats;
+  const float* ln_shift;
+  const float* ln_scale;
+  int ln_pitch, ln_rows;
+  int split_ea;
+  void* as;
+  void* c_split;
+  int c_split_ea;
+  void* ap_q;
+  void* ap_k;
+  void* ap_v;
+  int ap_vonly, ap_L, ap_heads, ap_Dh, ap_legacy;
+  float ap_alpha, ap_bscale;
+  int ap_ea, ap_eb, ap_ev;
+  int* range_flag;
+};
+
+extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  auto bad_arg = [&](const char* m) {
+    set_error(m);
+    return DM_ERR_ARG;
+  };
+  if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || !d->W) return bad_arg("token gemm: empty problem");
+  if (d->path < 0 || d->path > 2 || d->a_form < 0 || d->a_form > 2) return bad_arg("token gemm: path 0..2, a_form 0..2");
+  if (d->a_form != 2 && !d->A) return bad_arg("token gemm: A");
+  if (d->a_form != 0 && !d->as) return bad_arg("token gemm: a_form 1 / 2 need the `as` buffer");
+  if (!d->C && !d->c_split && !d->ap_q) return bad_arg("token gemm: no output");
+  if (d->ln_stats && !(d->ln_shift && d->ln_scale && d->ln_rows > 0 && d->ln_pitch >= d->K))
+    return bad_arg("token gemm: LayerNorm prologue tables");
+  if (d->pro_scale && !(d->pro_shift && d->pro_rows > 0)) return bad_arg("token gemm: GroupNorm prologue tables");
+  if (d->gate && !(d->res && d->gate_rows > 0 && d->gate_pitch >= d->N)) return bad_arg("token gemm: gate");
+  if (d->res && d->ld_res < d->N) return bad_arg("token gemm: residual pitch");
+  if (d->C && d->ldc < d->N) return bad_arg("token gemm: output pitch");
+  if (d->ap_q) {  // the planes' own geometry (the plans guarantee it; linear_k32_ok checks the column groups)
+    const long C = (long)d->ap_heads * d->ap_Dh;
+    if (!(d->ap_k && d->ap_v && d->ap_L > 0 && d->ap_L % 8 == 0 && d->M % d->ap_L == 0 && d->ap_heads > 0 &&
+          d->ap_Dh > 0 && d->N == (d->ap_vonly ? C : 3 * C)))
+      return bad_arg("token gemm: attention plane geometry");
+  }
+  if (d->path != 0 && (d->a_form == 2 || d->c_split || d->ap_q || d->sk)) {
+    set_error("token gemm: pre-split input, c_split, planes and split-K are linear_k32 forms");
+    return DM_ERR_UNSUPPORTED;
+  }
+  GemmArgs g{};
+  g.M = d->M; g.N = d->N; g.K = d->K; g.Z1 = 1; g.Z2 = 1;
+  g.A = d->A; g.lda = d->lda; g.Bm = d->W; g.ldb = d->K; g.C = d->C; g.ldc = d->ldc; g.alpha = d->alpha;
+  g.bias = d->bias; g.res = d->res; g.ld_res = d->ld_res; g.res_mod = d->res_mod;
+  g.gate = d->gate; g.gate_pitch = d->gate_pitch; g.gate_rows = d->gate_rows; g.act = d->act;
+  g.pro_scale = d->pro_scale; g.pro_shift = d->pro_shift; g.pro_rows = d->pro_rows;
+  g.ln_stats = (const float2*)d->ln_stats; g.ln_shift = d->ln_shift; g.ln_scale = d->ln_scale;
+  g.ln_pitch = d->ln_pitch; g.ln_rows = d->ln_rows;
+  g.split = d->path == 2 ? 0 : 2; g.split_ea = d->split_ea;
+  g.c_split = (_Float16*)d->c_split; g.c_split_ea = d->c_split_ea;
+  g.ap_q = (_Float16*)d->ap_q; g.ap_k = (_Float16*)d->ap_k; g.ap_v = (_Float16*)d->ap_v;
+  g.ap_vonly = d->ap_vonly; g.ap_L = d->ap_L; g.ap_heads = d->ap_heads; g.ap_Dh = d->ap_Dh; g.ap_legacy = d->ap_legacy;
+  g.ap_alpha = d->ap_alpha; g.ap_bscale = d->ap_bscale; g.ap_ea = d->ap_ea; g.ap_eb = d->ap_eb; g.ap_ev = d->ap_ev;
+  g.range_flag = d->range_flag;
+  void* ws = nullptr;
+  float* skw = nullptr;
+  unsigned* skc = nullptr;
+  int rc = DM_OK;
+  auto fail = [&](const char* m) {
+    set_error(m);
+    return DM_ERR_HIP;
+  };
+  do {
+    GemmArgs gp = g;  // the pre-split pass: the prologue, alpha and the split of A
+    if (d->path == 0) {
+      if (d->K % 64 != 0) { set_error("token gemm: linear_k32 needs K % 64 == 0"); rc = DM_ERR_UNSUPPORTED; break; }
+      if (hipMalloc(&ws, split_conv_weights_bytes(1, d->N, d->K, 2)) != hipSuccess) { rc = fail("alloc"); break; }
+      g.ws = ws; g.ws_rowscale = split_conv_rowscale(ws, 1, d->N, d->K);
+      if (d->a_form != 0) {
+        g.as = (const _Float16*)d->as;
+        if (d->a_form == 1) {
+          g.pro_scale = g.pro_shift = nullptr;
+          g.ln_stats = nullptr;
+        }
+      }
+      if (!linear_k32_ok(g)) { set_error("token gemm: linear_k32_ok refuses the descriptor"); rc = DM_ERR_UNSUPPORTED; break; }
+      if ((rc = split_conv_weights(d->W, 1, d->N, d->K, d->K, 1, 2, ws, st)) != DM_OK) break;
+      if (d->sk) {
+        const int slots = linear_k32_slots();
+        if (slots <= 0) { rc = fail("no occupancy"); break; }
+        if (hipMalloc(&skw, (size_t)slots * 65536) != hipSuccess || hipMalloc(&skc, (size_t)slots * 4) != hipSuccess ||
+            hipMemsetAsync(skc, 0, (size_t)slots * 4, st) != hipSuccess) { rc = fail("alloc"); break; }
+        g.sk_ws = skw; g.sk_cnt = skc; g.sk_cap = slots;
+      }
+    } else if (d->path == 1) {
+      if (hipStreamSynchronize(st) != hipSuccess) { rc = fail("sync"); break; }
+      g.split_eb = split_weight_exponent(d->W, (size_t)d->N * d->K);
+    }
+    if (d->a_form == 1 && (rc = linear_presplit_a(gp, (_Float16*)d->as, st)) != DM_OK) break;
+    if ((rc = gemm_batched(g, st)) != DM_OK) break;
+    if (hipStreamSynchronize(st) != hipSuccess) rc = fail("sync");
+  } while (false);
+  (void)hipStreamSynchronize(st);
+  if (ws) (void)hipFree(ws);
+  if (skw) (void)hipFree(skw);
+  if (skc) (void)hipFree(skc);
+  return rc;
+}
