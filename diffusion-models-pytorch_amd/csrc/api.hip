@@ -89,9 +89,9 @@ extern "C" const char* dm_last_error(void) { return dm::last_error(); }
 #endif
 extern "C" const char* dm_build_info(void) { return "src=" DM_SRC_HASH " arch=gfx950"; }
 
-extern "C" int dm_sampler_step(const dm_step_desc* d, void* stream) {
+// dm_step_desc -> StepArgs, with the descriptor's argument checks
+static int step_args_from_desc(const dm_step_desc* d, dm::StepArgs& s) {
   if (!d) { dm::set_error("null step descriptor"); return DM_ERR_ARG; }
-  dm::StepArgs s{};
   s.B = d->B; s.C = d->C; s.HW = d->HW; s.Cm = d->Cm;
   s.xt = d->xt; s.out_c = d->model_out; s.out_u = d->model_out_uncond;
   s.w_u = d->w_uncond; s.w_c = d->w_cond;
@@ -111,13 +111,64 @@ extern "C" int dm_sampler_step(const dm_step_desc* d, void* stream) {
   if (s.objective < 0 || s.objective > 2) { dm::set_error("invalid objective"); return DM_ERR_ARG; }
   if (s.kind < 0 || s.kind > 1) { dm::set_error("invalid sampler kind"); return DM_ERR_ARG; }
   if (s.B < 0 || s.C <= 0 || s.HW <= 0) { dm::set_error("invalid shape"); return DM_ERR_ARG; }
+  return DM_OK;
+}
+
+extern "C" int dm_sampler_step(const dm_step_desc* d, void* stream) {
+  dm::StepArgs s{};
+  if (const int rc = step_args_from_desc(d, s); rc != DM_OK) return rc;
   return dm::sampler_step(s, (hipStream_t)stream);
+}
+
+struct dm_lowpass {
+  dm::Lowpass lp;
+};
+
+extern "C" int dm_lowpass_create(int H, int W, int N, const float* const* weights, const int32_t* const* left,
+                                 const int* taps, void* stream, dm_lowpass** out) {
+  if (!weights || !left || !taps || !out) { dm::set_error("low-pass plan: null argument"); return DM_ERR_ARG; }
+  dm::Lowpass lp{};
+  const int rc = dm::lowpass_create(H, W, N, weights, left, taps, (hipStream_t)stream, &lp);
+  if (rc != DM_OK) return rc;
+  *out = new dm_lowpass{lp};
+  return DM_OK;
+}
+
+extern "C" int64_t dm_lowpass_scratch_bytes(const dm_lowpass* p, int64_t planes) {
+  if (!p || planes < 0) return -1;
+  return (int64_t)dm::lowpass_scratch_floats(p->lp, (long)planes) * (int64_t)sizeof(float);
+}
+
+extern "C" int dm_lowpass_apply(const dm_lowpass* p, const float* x, float* y, int64_t planes, void* scratch,
+                                void* stream) {
+  if (!p) { dm::set_error("low-pass filter: null plan"); return DM_ERR_ARG; }
+  return dm::lowpass_apply(p->lp, x, y, (long)planes, (float*)scratch, (hipStream_t)stream);
+}
+
+extern "C" void dm_lowpass_destroy(dm_lowpass* p) {
+  if (!p) return;
+  dm::lowpass_destroy(&p->lp);
+  delete p;
+}
+
+extern "C" int dm_guided_step(const dm_step_desc* d, const dm_guide_desc* g, void* stream) {
+  dm::StepArgs s{};
+  if (const int rc = step_args_from_desc(d, s); rc != DM_OK) return rc;
+  if (!g) { dm::set_error("null guide descriptor"); return DM_ERR_ARG; }
+  dm::GuideArgs a{};
+  a.kind = g->kind;
+  a.known = g->known; a.eps_k = g->noise_known_eps; a.noise_known = g->noise_known;
+  a.c_a = g->sqrt_ac_prev; a.c_b = g->sqrt_one_minus_ac_prev;
+  a.mask = g->mask; a.mask_c = g->mask_channels;
+  a.lp = g->lowpass ? &g->lowpass->lp : nullptr;
+  a.scratch = (float*)g->scratch;
+  return dm::guided_step(s, a, (hipStream_t)stream);
 }
 
 extern "C" int dm_lincomb(int mode, const float* a, const float* b, float* out, int64_t n, int64_t row_elems,
                           const float* c1_rows, const float* c2_rows, float c1, float c2, void* stream) {
   if (!a || !b || !out) { dm::set_error("null tensor"); return DM_ERR_ARG; }
-  if (mode < 0 || mode > 2) { dm::set_error("lincomb mode must be 0, 1 or 2"); return DM_ERR_ARG; }
+  if (mode < 0 || mode > 3) { dm::set_error("lincomb mode must be 0 .. 3"); return DM_ERR_ARG; }
   if (n < 0 || row_elems <= 0) { dm::set_error("invalid shape"); return DM_ERR_ARG; }
   return dm::lincomb(mode, a, b, out, (long)n, (long)row_elems, c1_rows, c2_rows, c1, c2, (hipStream_t)stream);
 }

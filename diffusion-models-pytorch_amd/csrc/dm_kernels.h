@@ -457,7 +457,7 @@ struct GnFin {
 int conv3x3_small_out(const View& x, const float* wp, const float* bias, int Cout, float* y, hipStream_t st,
                       const float* pro_scale = nullptr, const float* pro_shift = nullptr, const GnFin& fin = GnFin{});
 int sampler_step(const StepArgs& s, hipStream_t st);
-// out = c1 a + c2 b (mode 0), c1 a - c2 b (1), (c1 a - b) / c2 (2); per-row coefficients when c*_rows given
+// out = c1 a + c2 b (mode 0), c1 a - c2 b (1), (c1 a - b) / c2 (2), (a - c1 b) / c2 (3); per-row coefficients when c*_rows given
 int lincomb(int mode, const float* a, const float* b, float* out, long n, long row_elems, const float* c1_rows,
             const float* c2_rows, float c1, float c2, hipStream_t st);
 int nchw_to_nhwc(const float* x, int B, int C, int HW, float* y, int y_pitch, hipStream_t st);
@@ -465,5 +465,39 @@ int nhwc_to_nchw(const float* x, int B, int C, int HW, int pitch, float* y, hipS
 int repack_conv(const float* w, int Cout, int Cin, int taps, float* out, int ldw, int col0, hipStream_t st);
 // torch 3x3 weight [Cout][Cin][3][3] -> sub-pixel upsample weights [4 parities][Cout][4 * Cin]
 int repack_subpixel(const float* w, int Cout, int Cin, float* out, hipStream_t st);
+
+// ---------------------------------------------------------------- guided sampling (guidance.hip)
+// One axis of the separable resize: out[o] = sum_k w[o * taps + k] * in[left[o] + k], taps outside [0, n_in)
+// read the zero padding (reference utils/resize_right: field of view + normalised weights, built on the host).
+struct AxisTable {
+  const float* w;
+  const int* left;
+  int n_out, n_in, taps;
+};
+// ILVR low-pass plan: down-H, down-W, up-H, up-W tables of an H x W plane at factor N (device memory).
+struct Lowpass {
+  int H, W, N;
+  AxisTable dh, dw, uh, uw;
+  void* dev;  // the allocation the tables live in
+};
+int lowpass_create(int H, int W, int N, const float* const w[4], const int* const left[4], const int taps[4],
+                   hipStream_t st, Lowpass* out);
+void lowpass_destroy(Lowpass* lp);
+// floats of scratch the two-launch path needs for `planes` planes (0: the one-launch path serves the shape)
+long lowpass_scratch_floats(const Lowpass& lp, long planes);
+int lowpass_apply(const Lowpass& lp, const float* x, float* y, long planes, float* scratch, hipStream_t st);
+
+struct GuideArgs {
+  int kind;              // 1 mask, 2 ILVR
+  const float* known;    // masked image / reference images [B, C, HW]
+  const float* eps_k;    // noise that diffuses `known` to t_prev (noise_known) or null
+  int noise_known;       // t != 0
+  float c_a, c_b;        // sqrt(ac_prev), sqrt(1 - ac_prev)
+  const float* mask;     // [B, mask_c, HW], mask_c 1 or C
+  int mask_c;
+  const Lowpass* lp;
+  float* scratch;
+};
+int guided_step(const StepArgs& s, const GuideArgs& g, hipStream_t st);
 
 }  // namespace dm

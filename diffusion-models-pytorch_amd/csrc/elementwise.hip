@@ -14,6 +14,7 @@
 #include "dm_common.h"
 #include "dm_kernels.h"
 #include "mfma_tile.h"
+#include "sampler_step.h"
 
 namespace dm {
 
@@ -413,29 +414,8 @@ __global__ void sampler_step_kernel(StepArgs s) {
   const long mo = b * (long)s.Cm * s.HW + r;  // model-output index of the first C channels
   const float xt = s.xt[e];
 
-  // predict(): model output -> (x0, eps) for one branch, reference ddpm.py:174-203
-  auto predict = [&](float out, int objective, float& x0, float& eps) {
-    if (objective == 0) {
-      x0 = s.c_recip * xt - s.c_recipm1 * out;
-    } else if (objective == 1) {
-      x0 = out;
-    } else {
-      x0 = s.c_sa * xt - s.c_s1ma * out;
-    }
-    if (s.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
-    eps = (s.c_recip * xt - x0) / s.c_recipm1;
-  };
-
   float x0, eps;
-  if (s.out_u) {
-    float x0c, epsc, x0u, epsu;
-    predict(s.out_c[mo], s.objective, x0c, epsc);
-    predict(s.out_u[mo], s.objective, x0u, epsu);
-    const float comb = s.w_u * epsu + s.w_c * epsc;
-    predict(comb, 0, x0, eps);  // hack_objective('pred_eps')
-  } else {
-    predict(s.out_c[mo], s.objective, x0, eps);
-  }
+  step_predict(s, e, mo, xt, x0, eps);  // sampler_step.h
 
   if (s.euler) {
     // euler.py:60-64 / heun.py:66-70 (first order), heun.py:89-100 (second order), reference op order
@@ -457,33 +437,7 @@ __global__ void sampler_step_kernel(StepArgs s) {
     if (s.eps_out) s.eps_out[e] = eps;
     return;
   }
-  float mean, sample;
-  if (s.kind == 0) {
-    mean = s.m1 * x0 + s.m2 * eps;  // ddim.py:72-73
-  } else {
-    mean = s.m1 * x0 + s.m2 * xt;   // ddpm.py:230
-  }
-  float var = 0.f;
-  float sd = s.std;
-  if (s.var_mode == 1 && s.add_noise) {
-    // learned_range, ddpm.py:240-246; learned channel comes from the cond branch
-    const float lv = s.out_c[mo + per];
-    const float frac = (lv + 1.0f) / 2.0f;
-    const float logvar = frac * s.max_logvar + (1.0f - frac) * s.min_logvar;
-    var = expf(logvar);
-    sd = sqrtf(var);
-  }
-  if (s.add_noise) {
-    const float nz = s.noise ? s.noise[e] : 0.f;
-    sample = mean + sd * nz;
-  } else {
-    sample = mean;
-  }
-  s.sample[e] = sample;
-  if (s.mean_out) s.mean_out[e] = mean;
-  if (s.x0_out) s.x0_out[e] = x0;
-  if (s.eps_out) s.eps_out[e] = eps;
-  if (s.var_out) s.var_out[e] = var;
+  s.sample[e] = step_update(s, e, mo, per, xt, x0, eps);
 }
 
 // Two-operand combination with scalar or per-row coefficients, each product and the final add / sub / div
@@ -491,6 +445,7 @@ __global__ void sampler_step_kernel(StepArgs s) {
 //   mode 0: c1 a + c2 b        diffuse (:164-172), pred_eps_from_v (:117-120)
 //   mode 1: c1 a - c2 b        pred_x0_from_eps (:102-105), pred_x0_from_v (:112-115), get_v (:140-150)
 //   mode 2: (c1 a - b) / c2    pred_eps_from_x0 (:107-110)
+//   mode 3: (a - c1 b) / c2    pred_x0_from_mu (guidance/base.py:38-45)
 // Row r = e / row_elems selects c1_rows[r] / c2_rows[r] when given (per-image timesteps).
 __global__ void lincomb_kernel(int mode, const float* __restrict__ a, const float* __restrict__ b,
                                float* __restrict__ out, long n, long row_elems, const float* __restrict__ c1r,
@@ -505,8 +460,10 @@ __global__ void lincomb_kernel(int mode, const float* __restrict__ a, const floa
     v = pa + k2 * b[e];
   } else if (mode == 1) {
     v = pa - k2 * b[e];
-  } else {
+  } else if (mode == 2) {
     v = (pa - b[e]) / k2;
+  } else {
+    v = (a[e] - k1 * b[e]) / k2;
   }
   out[e] = v;
 }
@@ -762,7 +719,7 @@ int sampler_step(const StepArgs& s, hipStream_t st) {
 
 int lincomb(int mode, const float* a, const float* b, float* out, long n, long row_elems, const float* c1_rows,
             const float* c2_rows, float c1, float c2, hipStream_t st) {
-  DM_REQUIRE(mode >= 0 && mode <= 2, "lincomb: mode must be 0, 1 or 2");
+  DM_REQUIRE(mode >= 0 && mode <= 3, "lincomb: mode must be 0 .. 3");
   DM_REQUIRE(a && b && out && n >= 0 && row_elems > 0, "lincomb: null tensor or bad shape");
   if (n == 0) return DM_OK;
   hipLaunchKernelGGL(lincomb_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mode, a, b, out, n,

@@ -208,7 +208,9 @@ class DDPM:
               model_output_uncond: Tensor = None, guidance_scale: float = 1.0,
               objective: str = None, want_noise: bool = True, predict_only: bool = False,
               coefs: dict = None, euler: int = 0, ecoefs: dict = None, d1: Tensor = None, x1: Tensor = None,
-              dout: Tensor = None):
+              dout: Tensor = None, guide: Callable = None):
+        # guide: () -> (dmhip.GuideDesc, tensors it points to), called after reverse_eps is drawn (the
+        # reference's noise order); the update and the guidance then run as dm_guided_step
         dmhip.require_device_tensor(xt, 'xt')
         dmhip.require_device_tensor(model_output, 'model_output')
         if model_output_uncond is not None:
@@ -260,7 +262,12 @@ class DDPM:
             d.e_d1 = d1.data_ptr() if d1 is not None else None
             d.e_x1 = x1.data_ptr() if x1 is not None else None
             d.e_dout = dout.data_ptr() if dout is not None else None
-        dmhip.sampler_step(d, xt.device)
+        if guide is None:
+            dmhip.sampler_step(d, xt.device)
+        else:
+            gdesc, keep = guide()
+            dmhip.guided_step(d, gdesc, xt.device)
+            del keep
         if learned:
             var = var_t
         else:

@@ -82,6 +82,15 @@ class StepDesc(ctypes.Structure):
     ]
 
 
+class GuideDesc(ctypes.Structure):
+    """dm_guide_desc (include/dm_hip.h)."""
+    _fields_ = [
+        ('kind', ctypes.c_int), ('known', vp), ('noise_known', ctypes.c_int), ('noise_known_eps', vp),
+        ('sqrt_ac_prev', ctypes.c_float), ('sqrt_one_minus_ac_prev', ctypes.c_float),
+        ('mask', vp), ('mask_channels', ctypes.c_int), ('lowpass', vp), ('scratch', vp),
+    ]
+
+
 class ConvDesc(ctypes.Structure):
     _fields_ = [
         ('x', vp), ('x_pitch', ctypes.c_int), ('Cin', ctypes.c_int), ('Hin', ctypes.c_int), ('Win', ctypes.c_int),
@@ -284,6 +293,14 @@ def _declare(L: ctypes.CDLL):
     L.dm_dit_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     L.dm_lincomb.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_float,
                              ctypes.c_float, vp]
+    L.dm_guided_step.argtypes = [ctypes.POINTER(StepDesc), ctypes.POINTER(GuideDesc), vp]
+    L.dm_lowpass_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                    ctypes.POINTER(ctypes.c_int), vp, ctypes.POINTER(vp)]
+    L.dm_lowpass_scratch_bytes.argtypes = [vp, ctypes.c_int64]
+    L.dm_lowpass_scratch_bytes.restype = ctypes.c_int64
+    L.dm_lowpass_apply.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp]
+    L.dm_lowpass_destroy.argtypes = [vp]
+    L.dm_lowpass_destroy.restype = None
     L.dm_comm_unique_id.argtypes = [vp]
     L.dm_comm_init.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     L.dm_comm_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
@@ -356,6 +373,57 @@ def _p(t: Optional[torch.Tensor]):
 # --------------------------------------------------------------------------- ops
 def sampler_step(desc: StepDesc, device=None):
     check(load().dm_sampler_step(ctypes.byref(desc), stream_handle(device)), 'dm_sampler_step')
+
+
+def guided_step(desc: StepDesc, guide: GuideDesc, device=None):
+    check(load().dm_guided_step(ctypes.byref(desc), ctypes.byref(guide), stream_handle(device)), 'dm_guided_step')
+
+
+class LowpassPlan:
+    """dm_lowpass: the four axis tables of ILVR's low-pass filter on one device. `tables` are the host
+    tables in pass order (down-H, down-W, up-H, up-W), each (weights [n_out, taps] float32, left [n_out] int32)
+    CPU tensors (diffusions/guidance/lowpass.py axis_tables)."""
+
+    def __init__(self, H: int, W: int, N: int, tables, device):
+        self.H, self.W, self.N = int(H), int(W), int(N)
+        self.device = torch.device(device)
+        keep = [(w.to(torch.float32).contiguous(), l.to(torch.int32).contiguous()) for w, l in tables]
+        if len(keep) != 4:
+            raise ValueError('a low-pass plan takes four axis tables')
+        wp = (vp * 4)(*[w.data_ptr() for w, _ in keep])
+        lp = (vp * 4)(*[l.data_ptr() for _, l in keep])
+        taps = (ctypes.c_int * 4)(*[w.shape[1] for w, _ in keep])
+        n_out = (self.H // self.N, self.W // self.N, self.H, self.W) if self.N > 0 else None
+        if n_out is not None and any(w.shape[0] != n or l.shape != (n, ) for (w, l), n in zip(keep, n_out)):
+            raise ValueError('low-pass tables do not match H, W and N')
+        self.handle = vp()
+        with torch.cuda.device(self.device):
+            check(load().dm_lowpass_create(self.H, self.W, self.N, wp, lp, taps, stream_handle(self.device),
+                                           ctypes.byref(self.handle)), 'dm_lowpass_create')
+
+    def scratch(self, planes: int) -> Optional[torch.Tensor]:
+        """The scratch tensor a call over `planes` planes needs (None for one-launch shapes)."""
+        n = load().dm_lowpass_scratch_bytes(self.handle, planes)
+        if n < 0:
+            raise DMError('dm_lowpass_scratch_bytes failed')
+        return torch.empty(n, dtype=torch.uint8, device=self.device) if n else None
+
+    def apply(self, x: torch.Tensor) -> torch.Tensor:
+        """phi(x) for x [..., H, W] (a contiguous float32 device tensor)."""
+        require_device_tensor(x, 'x')
+        if x.ndim < 2 or tuple(x.shape[-2:]) != (self.H, self.W):
+            raise ValueError(f'low-pass plan is for {self.H} x {self.W} planes, got {tuple(x.shape)}')
+        planes = x.numel() // (self.H * self.W)
+        y = torch.empty_like(x)
+        scratch = self.scratch(planes)
+        check(load().dm_lowpass_apply(self.handle, x.data_ptr(), y.data_ptr(), planes, _p(scratch),
+                                      stream_handle(x.device)), 'dm_lowpass_apply')
+        return y
+
+    def __del__(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h and _lib is not None:
+            _lib.dm_lowpass_destroy(h)
 
 
 def groupnorm_nhwc(x: torch.Tensor, y: torch.Tensor, B: int, HW: int, C: int, G: int, eps: float,
@@ -535,7 +603,8 @@ def share_workspace(a, b):
 
 
 def lincomb(mode: int, a: torch.Tensor, b: torch.Tensor, c1, c2, out: torch.Tensor = None) -> torch.Tensor:
-    """out = c1 a + c2 b (mode 0), c1 a - c2 b (1), (c1 a - b) / c2 (2) on device tensors of one shape;
+    """out = c1 a + c2 b (mode 0), c1 a - c2 b (1), (c1 a - b) / c2 (2), (a - c1 b) / c2 (3) on device tensors of one
+    shape;
     c1 / c2 are python floats (rounded to float32) or [B] float32 device tensors (one per image, dim 0)."""
     for name, t in (('a', a), ('b', b)):
         require_device_tensor(t, name)

@@ -124,3 +124,15 @@ def sample_folds(sample_fn: Callable[[torch.Tensor], torch.Tensor], img_shape, n
             sink(idx, samples)
         idx += bs
     return folds
+
+
+def dataset_rounds(n: int, batch_size: int, world: int, rank: int):
+    """Batches of an n-item dataset dealt to ranks round-robin, as accelerate's prepared DataLoader does (batch
+    k * world + rank, the last round padded by wrapping to the start like even_batches). Yields per round
+    (this rank's item ids, number of gathered items to keep: gather_for_metrics drops the padding)."""
+    bspp = min(batch_size, math.ceil(n / world))
+    n_batches = math.ceil(n / bspp)
+    for rnd in range(math.ceil(n_batches / world)):
+        lo = (rnd * world + rank) * bspp
+        ids = [(lo + j) % n for j in range(bspp)]
+        yield ids, max(0, min(n - rnd * world * bspp, world * bspp))

@@ -248,10 +248,52 @@ int dm_sampler_step(const dm_step_desc* d, void* stream);
  *                                   pred_eps_from_v (:117-120)
  *   mode 1: out = c1 a - c2 b       pred_x0_from_eps (:102-105), pred_x0_from_v (:112-115), get_v (:140-150)
  *   mode 2: out = (c1 a - b) / c2   pred_eps_from_x0 (:107-110)
+ *   mode 3: out = (a - c1 b) / c2   pred_x0_from_mu (diffusions/guidance/base.py:38-45: (mu - coef2 xt) / coef1)
  * a, b, out: n floats; c1_rows / c2_rows: per-row coefficients (row = element / row_elems, one row per image
  * with its own timestep) or NULL for the scalars c1 / c2. */
 int dm_lincomb(int mode, const float* a, const float* b, float* out, int64_t n, int64_t row_elems,
                const float* c1_rows, const float* c2_rows, float c1, float c2, void* stream);
+
+/* Guided sampling -----------------------------------------------------------
+ * Reference diffusions/guidance/: MaskGuidance (inpainting, RePaint) and ILVR act on the sampled x_{t-1}
+ * (cond_fn_sample). dm_guided_step is dm_sampler_step's DDPM / DDIM update (euler = 0) fused with that guidance:
+ * `sample` receives the guided x_{t-1}; mean / pred_x0 / pred_eps / var come out as from dm_sampler_step.
+ *
+ * Low-pass plan (ILVR's phi = resize(resize(x, 1/N), N) of utils/resize_right, ilvr.py:48-52): the resize is
+ * separable and linear, per axis out[o] = sum_k weights[o][k] * in[left[o] + k] with zero padding outside the
+ * axis. The host computes the four tables -- 0 down-H (H/N outputs over H inputs), 1 down-W, 2 up-H (H outputs over
+ * H/N inputs), 3 up-W -- with the reference's op sequence (diffusions/guidance/lowpass.py does) and passes them as
+ * host arrays: weights[i] is [n_out_i][taps[i]] float32, left[i] is [n_out_i] int32 (may be negative). The plan
+ * copies them to the device; H and W up to 256, N any common divisor. The passes run in the reference's order
+ * (down-H, down-W, up-H, up-W), each output an fp32 sum over its taps in tap order.
+ * dm_lowpass_apply filters `planes` H x W planes (x -> y, not in place). Planes up to 64 x 64 take one launch with
+ * every intermediate in LDS (dm_lowpass_scratch_bytes = 0, scratch may be NULL); larger ones two launches with the
+ * H/N x W/N intermediate in `scratch` (dm_lowpass_scratch_bytes(plan, planes) bytes, at most 1/N^2 of the planes). */
+typedef struct dm_lowpass dm_lowpass;
+int dm_lowpass_create(int H, int W, int N, const float* const* weights, const int32_t* const* left, const int* taps,
+                      void* stream, dm_lowpass** out);
+int64_t dm_lowpass_scratch_bytes(const dm_lowpass* plan, int64_t planes);
+int dm_lowpass_apply(const dm_lowpass* plan, const float* x, float* y, int64_t planes, void* scratch, void* stream);
+void dm_lowpass_destroy(dm_lowpass* plan);
+
+typedef struct dm_guide_desc {
+  int kind;                     /* 1: mask (mask_guidance.py:52-62), 2: ILVR (ilvr.py:38-46) */
+  const float* known;           /* masked image (kind 1) / reference images (kind 2), [B, C, HW] */
+  int noise_known;              /* t != 0: the guidance uses q(x_{t_prev} | known) = sqrt_ac_prev * known +
+                                   sqrt_one_minus_ac_prev * noise_known_eps; 0: `known` itself */
+  const float* noise_known_eps; /* [B, C, HW] (noise_known != 0) */
+  float sqrt_ac_prev, sqrt_one_minus_ac_prev;  /* host coefficients, as dm_step_desc's */
+  /* kind 1: sample + (noisy_known - sample) * mask, products separately rounded (bit-identical to the torch
+   * expression); mask [B, mask_channels, HW] with mask_channels 1 or C, any float values */
+  const float* mask;
+  int mask_channels;
+  /* kind 2: sample + phi(noisy_ref - sample) (= sample + phi(noisy_ref) - phi(sample) by linearity), the plan
+   * for the image's H x W (H * W == dm_step_desc.HW); scratch: dm_lowpass_scratch_bytes(plan, B * C) bytes or NULL
+   * when that is 0. One launch for planes up to 64 x 64, else two; noisy_ref and the difference stay on chip. */
+  const dm_lowpass* lowpass;
+  void* scratch;
+} dm_guide_desc;
+int dm_guided_step(const dm_step_desc* d, const dm_guide_desc* g, void* stream);
 
 /* Operator-level entry points (NHWC, channel-pitched views) ----------------
  * Used by the parity tests and to compose other denoisers.
