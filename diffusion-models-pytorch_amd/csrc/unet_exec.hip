@@ -23,69 +23,11 @@
 #include "dm_common.h"
 #include "dm_kernels.h"
 #include "plan.h"
+#include "exec_pack.h"
 
 namespace dm {
 
 namespace {
-
-struct ParamReader {
-  const float* const* params;
-  const int64_t* numels;
-  int n, pos = 0;
-  std::string err;
-  const float* take(int64_t expect, const char* what) {
-    if (pos >= n) {
-      if (err.empty()) err = std::string("too few parameters at ") + what;
-      return nullptr;
-    }
-    if (numels[pos] != expect && err.empty())
-      err = "parameter " + std::to_string(pos) + " (" + what + "): expected " + std::to_string(expect) +
-            " elements, got " + std::to_string(numels[pos]);
-    return params[pos++];
-  }
-};
-
-// A copy / repack job into the weight arena.
-struct PackJob {
-  int kind;  // 0 raw copy, 1 conv repack, 2 add (bias sum), 3 sub-pixel upsample repack
-  const float* src;
-  const float* src2;
-  int64_t n;
-  int Cout, Cin, taps, ldw, col0;
-  size_t dst;  // float offset in arena
-};
-
-struct Packer {
-  std::vector<PackJob> jobs;
-  size_t size = 0;
-  size_t reserve(int64_t n) {
-    size_t off = size;
-    size += ((size_t)n + 63) / 64 * 64;
-    return off;
-  }
-  size_t raw(const float* src, int64_t n) {
-    size_t off = reserve(n);
-    jobs.push_back({0, src, nullptr, n, 0, 0, 0, 0, 0, off});
-    return off;
-  }
-  void raw_at(const float* src, int64_t n, size_t off) { jobs.push_back({0, src, nullptr, n, 0, 0, 0, 0, 0, off}); }
-  void conv_at(const float* w, int Cout, int Cin, int taps, int ldw, int col0, size_t off) {
-    jobs.push_back({1, w, nullptr, (int64_t)Cout * Cin * taps, Cout, Cin, taps, ldw, col0, off});
-  }
-  void add_at(const float* a, const float* b, int64_t n, size_t off) {
-    jobs.push_back({2, a, b, n, 0, 0, 0, 0, 0, off});
-  }
-  size_t subpix(const float* w, int Cout, int Cin) {
-    const size_t off = reserve((int64_t)16 * Cout * Cin);
-    jobs.push_back({3, w, nullptr, (int64_t)Cout * Cin * 9, Cout, Cin, 9, 0, 0, off});
-    return off;
-  }
-};
-
-__global__ void vec_add_kernel(const float* a, const float* b, float* out, int64_t n) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = a[i] + b[i];
-}
 
 struct GnP { size_t g, b; int C; };
 struct ConvP {
@@ -338,23 +280,9 @@ const UNetModel::FoldW* UNetModel::fold_for(const AttnP& p) {
   return &(folds[p.wqkv] = f);
 }
 
-// fp16x2 attention GEMMs (gemm.hip SPLIT): A scaled by 2^ea, B by the weight's exponent (max |w| *
-// 2^eb in [2^13, 2^14)) or, for an activation B, 2^eb_act. Activations use fixed exponents that keep
-// their low fp16 pieces normal down to ~2^-8 while leaving headroom to 65504 / 2^e (the range flag
-// catches the rest): GroupNorm'd inputs, q, k, v and the attention output 2^6, softmax rows (<= 1) 2^14.
+// fp16x2 attention GEMMs: operand exponents (exec_pack.h split_gemm_args)
 void UNetModel::split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act) {
-  g.split = 0;
-  if (conv_math != 2) return;
-  int eb = eb_act;
-  if (weight) {
-    auto it = w_exp.find(weight);
-    if (it == w_exp.end()) it = w_exp.emplace(weight, split_weight_exponent(weight, weight_n)).first;
-    eb = it->second;
-  }
-  g.split = 2;
-  g.split_ea = ea;
-  g.split_eb = eb;
-  g.range_flag = range_flag;
+  split_gemm_args(g, conv_math, w_exp, range_flag, ea, weight, weight_n, eb_act);
 }
 
 // Channels of the first conv / last conv input: dim (models/unet.py:72) or
@@ -668,25 +596,8 @@ static int unet_create(const dm_unet_arch* arch, const float* const* params, con
   // allocate + run the pack jobs
   m->arena_floats = pk.size;
   DM_CHECK_HIP(hipMalloc(&m->arena, pk.size * sizeof(float)));
-  for (auto& j : pk.jobs) {
-    if (!j.src) {
-      set_error("null parameter pointer");
-      return DM_ERR_ARG;
-    }
-    if (j.kind == 0) {
-      DM_CHECK_HIP(hipMemcpyAsync(m->arena + j.dst, j.src, j.n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    } else if (j.kind == 1) {
-      rc = repack_conv(j.src, j.Cout, j.Cin, j.taps, m->arena + j.dst, j.ldw, j.col0, st);
-      if (rc) return rc;
-    } else if (j.kind == 3) {
-      rc = repack_subpixel(j.src, j.Cout, j.Cin, m->arena + j.dst, st);
-      if (rc) return rc;
-    } else {
-      hipLaunchKernelGGL(vec_add_kernel, dim3((unsigned)((j.n + 255) / 256)), dim3(256), 0, st, j.src, j.src2,
-                         m->arena + j.dst, j.n);
-      DM_LAUNCH_CHECK();
-    }
-  }
+  rc = run_pack_jobs(pk, m->arena, st);
+  if (rc) return rc;
   *out = m.release();
   return DM_OK;
 }

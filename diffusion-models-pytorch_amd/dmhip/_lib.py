@@ -62,6 +62,15 @@ class DiTArch(ctypes.Structure):
     ]
 
 
+class VaeArch(ctypes.Structure):
+    """dm_vae_arch (include/dm_hip.h)."""
+    _fields_ = [
+        ('z_channels', ctypes.c_int), ('out_channels', ctypes.c_int), ('ch', ctypes.c_int),
+        ('n_levels', ctypes.c_int), ('ch_mult', ctypes.c_int * DM_MAX_STAGES), ('num_res_blocks', ctypes.c_int),
+        ('norm_groups', ctypes.c_int), ('norm_eps', ctypes.c_float), ('post_quant', ctypes.c_int),
+    ]
+
+
 class StepDesc(ctypes.Structure):
     _fields_ = [
         ('B', ctypes.c_int), ('C', ctypes.c_int), ('HW', ctypes.c_int), ('Cm', ctypes.c_int),
@@ -288,6 +297,22 @@ def _declare(L: ctypes.CDLL):
     L.dm_dit_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.dm_dit_destroy.argtypes = [vp]
     L.dm_dit_destroy.restype = None
+    L.dm_vae_decoder_param_count.argtypes = [ctypes.POINTER(VaeArch), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_decoder_create.argtypes = [ctypes.POINTER(VaeArch), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_int, vp, ctypes.POINTER(vp)]
+    L.dm_vae_decoder_forward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp]
+    L.dm_vae_decoder_set_math.argtypes = [vp, ctypes.c_int]
+    L.dm_vae_decoder_get_math.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_decoder_range_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_decoder_profile.argtypes = [vp, ctypes.c_int]
+    L.dm_vae_decoder_profile_count.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_decoder_profile_get.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    L.dm_vae_decoder_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.dm_vae_decoder_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_decoder_destroy.argtypes = [vp]
+    L.dm_vae_decoder_destroy.restype = None
     L.dm_unet_share_workspace.argtypes = [vp, vp]
     L.dm_unet_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     L.dm_dit_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
@@ -512,6 +537,19 @@ def dit_math(handle, kind: Optional[str] = None) -> str:
     return {v: n for n, v in kinds.items()}[k.value]
 
 
+def vae_math(handle, kind: Optional[str] = None) -> str:
+    """Set (kind given) and return the arithmetic of a native VAE decoder handle: 'fp16x2' (default), 'bf16x3' or
+    'fp32' (dm_vae_decoder_set_math / dm_vae_decoder_get_math)."""
+    L = load()
+    if kind is not None:
+        if kind not in CONV_MATH:
+            raise ValueError(f'decoder math must be one of {sorted(CONV_MATH)}')
+        check(L.dm_vae_decoder_set_math(handle, CONV_MATH[kind]), 'dm_vae_decoder_set_math')
+    k = ctypes.c_int()
+    check(L.dm_vae_decoder_get_math(handle, ctypes.byref(k)), 'dm_vae_decoder_get_math')
+    return {v: n for n, v in CONV_MATH.items()}[k.value]
+
+
 def unet_conv_math(handle, kind: Optional[str] = None) -> str:
     """Set (kind given) and return the conv arithmetic of a native UNet handle: 'fp16x2' (default),
     'bf16x3' or 'fp32' (dm_unet_set_conv_math / dm_unet_get_conv_math)."""
@@ -543,7 +581,7 @@ def timestep_embedding(t: torch.Tensor, dim: int, kind: int, out: torch.Tensor, 
 
 
 def unet_profile_enable(handle, enable, abi: str = 'dm_unet'):
-    """Per-launch HIP-event profiling of a model's cached plan (abi: 'dm_unet' or 'dm_dit').
+    """Per-launch HIP-event profiling of a model's cached plan (abi: 'dm_unet', 'dm_dit' or 'dm_vae_decoder').
     enable: False/0 off, True/1 every forward, N > 1 every N-th forward."""
     check(getattr(load(), abi + '_profile')(handle, int(enable)), abi + '_profile')
 

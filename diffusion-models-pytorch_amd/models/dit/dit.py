@@ -2,9 +2,10 @@
 
 Same constructor (vae_config, vit_config, scale_factor) and forward
 (x, timesteps, y=None) -> vit(x, timesteps, y); state_dict loads go to the
-transformer, as upstream. The VAE (``AutoEncoderKL.from_pretrained``) is a
-network download in the reference and is outside the denoising hot path, so
-it is instantiated lazily, only when ``decode_latent`` is called.
+transformer, as upstream. The VAE (``models.dit.autoencoder.AutoEncoderKL``:
+the native latent decoder, built from a local checkpoint directory; a hub id
+raises NotImplementedError) is outside the denoising hot path, so it is
+instantiated lazily, only when ``decode_latent`` is called.
 """
 from typing import Any, Mapping
 

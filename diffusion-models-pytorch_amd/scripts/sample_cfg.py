@@ -20,9 +20,13 @@ page (streamlit/pages/2_Class_conditional_Image_Generation.py:46-60, 90-103):
 Multi-GPU follows sample_uncond's seed + rank sharding (the
 reference has no multi-GPU latent path): every rank samples bspp latents per
 fold and the fold is gathered once. Latents are decoded with the model's VAE
-when one can be built (`decode_latent`); the reference's VAE is a network
-download (models/dit/autoencoder.py), so without it the clamp-free latents are
-written as `{idx}.npy` (float32 [4, S, S]) instead of PNGs.
+when one can be built (`decode_latent`, the native decoder of
+models/dit/autoencoder.py): give the existing override
+`model.params.vae_config.params.from_pretrained=/path/to/dir` a local
+checkpoint directory in the diffusers layout (config.json +
+diffusion_pytorch_model.safetensors or .bin) and the script writes PNGs. The
+YAML's default is a hub id, which is never fetched: without a local directory
+the clamp-free latents are written as `{idx}.npy` (float32 [4, S, S]) instead.
 """
 import argparse
 import math

@@ -11,6 +11,10 @@ config overrides. Launch one process per GPU:
 `--weights synthetic` uses the deterministic synthetic weights (no checkpoint
 offline). Samplers: ddpm, ddim, euler, heun. Modes: sample, denoise, progressive, interpolate,
 reconstruction (DDIM inversion of the images under --input_dir, then sampling back).
+
+Latent denoisers (the DiT config) are sampled by scripts/sample_cfg.py, which builds its model with this
+script's `build_model`: the override `--model.params.vae_config.params.from_pretrained /path/to/dir` (a local
+diffusers-layout VAE directory) is all it takes for decoded PNGs; there is no new flag.
 """
 import argparse
 import math

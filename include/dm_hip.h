@@ -197,6 +197,51 @@ int dm_dit_memory(const dm_dit* m, int64_t* weight_bytes, int64_t* workspace_byt
 int dm_dit_plan_stats(const dm_dit* m, int64_t* builds, int* cached);
 void dm_dit_destroy(dm_dit* m);
 
+/* Latent decoder: KL autoencoder -------------------------------------------
+ * Replaces the decode path of the VAE the reference's DiT wraps (models/dit/autoencoder.py ->
+ * diffusers AutoencoderKL.decode; the same network as models/stablediffusion/autoencoder.py:376-483 Decoder and
+ * :522-525 AutoEncoderKL.decode): post_quant_conv, conv_in, mid.block_1 / attn_1 / block_2, per level
+ * num_res_blocks + 1 ResnetBlocks and an Upsample, norm_out, SiLU, conv_out. `params` are the tensors of the
+ * reference AutoEncoderKL.state_dict() in order, restricted to `decoder.*` followed (post_quant = 1) by
+ * `post_quant_conv.*`; the attention q / k / v / proj_out and post_quant_conv weights are [C][C] matrices (their
+ * 1x1 conv weights, same bytes). Channels of every level must be multiples of 32 (DM_ERR_ARG otherwise). */
+typedef struct dm_vae_arch {
+  int z_channels;      /* latent channels (1..4) */
+  int out_channels;    /* image channels (1..8) */
+  int ch;
+  int n_levels;        /* len(ch_mult) */
+  int ch_mult[DM_MAX_STAGES];
+  int num_res_blocks;  /* blocks per level are num_res_blocks + 1 */
+  int norm_groups;     /* 32 */
+  float norm_eps;      /* 1e-6 */
+  int post_quant;      /* 1: a 1x1 post_quant_conv z_channels -> z_channels runs first */
+} dm_vae_arch;
+
+typedef struct dm_vae_decoder dm_vae_decoder;
+
+int dm_vae_decoder_param_count(const dm_vae_arch* arch, int* n_params);
+int dm_vae_decoder_create(const dm_vae_arch* arch, const float* const* params, const int64_t* numels, int n_params,
+                          void* stream, dm_vae_decoder** out);
+/* z: [B, z_channels, H, W] f32 NCHW latents; out: [B, out_channels, H 2^(n_levels-1), W 2^(n_levels-1)] f32 NCHW,
+ * unclamped. The decoder runs on scale * z: `scale` is the float32 of the reference's `1. / scale_factor`
+ * (models/dit/dit.py decode_latent: `z = 1. / self.scale_factor * z`), multiplied in that operand order; 1.0f for
+ * latents the host has scaled already. Plans are cached per (B, H, W) as for dm_unet. */
+int dm_vae_decoder_forward(dm_vae_decoder* dec, const float* z, int B, int H, int W, float scale, float* out,
+                           void* stream);
+/* Arithmetic: DM_SPLIT_FP16X2 (default), DM_SPLIT_BF16X3, 0 = fp32 MFMA (also DM_CONV_MATH). An fp16x2 forward that
+ * meets an activation beyond the fp16 range is run again in bf16x3; the next forward is fp16x2 again.
+ * dm_vae_decoder_range_stats: forwards re-run so far and the arithmetic the next forward starts in. */
+int dm_vae_decoder_set_math(dm_vae_decoder* dec, int kind);
+int dm_vae_decoder_get_math(const dm_vae_decoder* dec, int* kind);
+int dm_vae_decoder_range_stats(const dm_vae_decoder* dec, int64_t* fallbacks, int* active_math);
+int dm_vae_decoder_profile(dm_vae_decoder* dec, int enable);
+int dm_vae_decoder_profile_count(dm_vae_decoder* dec, int* n_ops);
+int dm_vae_decoder_profile_get(dm_vae_decoder* dec, int i, char* label, int label_len, double* flops, double* bytes,
+                               double* ms_total, int64_t* launches);
+int dm_vae_decoder_memory(const dm_vae_decoder* dec, int64_t* weight_bytes, int64_t* workspace_bytes);
+int dm_vae_decoder_plan_stats(const dm_vae_decoder* dec, int64_t* builds, int* cached);
+void dm_vae_decoder_destroy(dm_vae_decoder* dec);
+
 /* Sampler update -----------------------------------------------------------
  * One elementwise pass doing predict() (ddpm.py:174-203), the optional CFG
  * combine (ddim.py:185 / ddpm.py:343-345, with the second predict under

@@ -1,0 +1,118 @@
+"""VAE latent decoder timing at the DiT-XL/2 geometry (sd-vae-ft architecture: ch 128, (1, 2, 4, 4), 2 blocks per
+level; 4 x 32 x 32 latents -> 256^2 images), synthetic weights (tests/vae_ref.py recipe).
+
+    python tools/vae_bench.py [--batches 8 16] [--iters 5] [--repeats 3] [--json out.json]
+
+Per batch size: the native decoder (dm_vae_decoder, one plan = one hipGraph) in ms/image and img/s, the median of
+`repeats` timed windows of `iters` decodes after a warm-up decode; then, in the same process on the same device, the
+comparison arm: tests/vae_ref.py's float32 torch graph run on the GPU through torch-ROCm (MIOpen / hipBLASLt), timed
+alike. The per-op profile (HIP events around each launch, a separate profiled run) and the workspace follow, with
+the middle attention's share of the decode time.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'diffusion-models-pytorch_amd')]
+
+import torch  # noqa: E402
+
+import dmhip  # noqa: E402
+from models.dit.autoencoder import AutoEncoderKL  # noqa: E402
+from tests import vae_ref  # noqa: E402
+
+
+def timed(fn, iters, repeats):
+    """Median over `repeats` windows of the mean ms of `iters` calls (device events)."""
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / iters)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batches', type=int, nargs='+', default=[8, 16])
+    ap.add_argument('--latent', type=int, default=32)
+    ap.add_argument('--iters', type=int, default=5)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--config', default='T3', choices=sorted(vae_ref.CONFIGS))
+    ap.add_argument('--no-torch', action='store_true', help='skip the torch-ROCm comparison arm')
+    ap.add_argument('--json', default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('vae_bench: no ROCm GPU visible (timings are taken on the GPU only)')
+    dev = torch.device('cuda', 0)
+    torch.set_grad_enabled(False)
+    sd = vae_ref.weights(args.config)
+    sd_dev = {k: v.to(dev) for k, v in sd.items()}
+    S = args.latent
+    result = dict(config=args.config, latent=S, runs=[])
+    for B in args.batches:
+        model = AutoEncoderKL.from_state_dict(vae_ref.diffusers_config(args.config), sd, decode_batch=B)
+        z = torch.randn((B, 4, S, S), generator=torch.Generator().manual_seed(1)).to(dev)
+        h = model.native_handle(dev)
+        med, lo, hi = timed(lambda: model.decode(z), args.iters, args.repeats)
+        w, ws = model.memory(dev)
+        run = dict(B=B, native_ms=med, native_ms_min=lo, native_ms_max=hi, native_ms_per_image=med / B,
+                   native_img_per_s=B / med * 1e3, weight_MiB=w / 2 ** 20, workspace_MiB=ws / 2 ** 20)
+        print(f'native  B={B:3d} {med:9.2f} ms/decode ({lo:.2f} .. {hi:.2f})  {med / B:8.3f} ms/image  '
+              f'{B / med * 1e3:8.1f} img/s  workspace {ws / 2 ** 20:.0f} MiB', flush=True)
+        if not args.no_torch:
+            out_t = vae_ref.decode(sd_dev, z)
+            err = (model.decode(z).sample - out_t).abs().max().item()
+            tm, tlo, thi = timed(lambda: vae_ref.decode(sd_dev, z), args.iters, args.repeats)
+            run.update(torch_ms=tm, torch_ms_min=tlo, torch_ms_max=thi, torch_ms_per_image=tm / B,
+                       torch_img_per_s=B / tm * 1e3, native_vs_torch_max_abs=err)
+            print(f'torch   B={B:3d} {tm:9.2f} ms/decode ({tlo:.2f} .. {thi:.2f})  {tm / B:8.3f} ms/image  '
+                  f'{B / tm * 1e3:8.1f} img/s  (native vs torch max-abs {err:.2e})', flush=True)
+            del out_t
+        # per-op profile, a run of its own
+        dmhip.unet_profile_enable(h, 1, 'dm_vae_decoder')
+        for _ in range(3):
+            model.decode(z)
+        torch.cuda.synchronize()
+        ops = dmhip.unet_profile_read(h, 'dm_vae_decoder')
+        dmhip.unet_profile_enable(h, 0, 'dm_vae_decoder')
+        total = sum(o['ms_total'] for o in ops)
+        fam = {}
+        for o in ops:
+            f = fam.setdefault(o['label'], dict(ms=0.0, n=0, flops=0.0))
+            f['ms'] += o['ms_total'] / max(o['launches'], 1)
+            f['n'] += 1
+            f['flops'] += o['flops']
+        # the middle attention's launches by position: [gn_*] qkv, per score chunk (S GEMM, softmax_rows, PV GEMM), proj
+        soft = [i for i, o in enumerate(ops) if o['label'] == 'softmax_rows']
+        lo_i, hi_i = soft[0] - 2, soft[-1] + 3
+        while lo_i > 0 and ops[lo_i - 1]['label'].startswith('gn_'):
+            lo_i -= 1
+        attn_ms = sum(o['ms_total'] / max(o['launches'], 1) for o in ops[lo_i:hi_i])
+        per_fwd = total / max(ops[0]['launches'], 1)
+        run.update(attention_ops=[o['label'] for o in ops[lo_i:hi_i]], profile_ms=per_fwd, attention_ms=attn_ms,
+                   attention_share=attn_ms / per_fwd, families=fam)
+        print(f'profile B={B}: {per_fwd:.2f} ms over {len(ops)} launches; middle attention {attn_ms:.3f} ms '
+              f'= {100 * attn_ms / per_fwd:.2f} %')
+        for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms']):
+            tf = v['flops'] / v['ms'] / 1e9 if v['ms'] > 0 else 0.0
+            print(f'  {v["ms"]:9.3f} ms {100 * v["ms"] / per_fwd:5.1f} %  x{v["n"]:3d}  {tf:7.1f} TFLOP/s  {k}')
+        result['runs'].append(run)
+        model.close()
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, 'w') as f:
+            json.dump(result, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
