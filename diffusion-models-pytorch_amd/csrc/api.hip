@@ -213,10 +213,15 @@ extern "C" int dm_pack_conv_weight(const float* w, int Cout, int Cin, int taps, 
   return dm::repack_conv(w, Cout, Cin, taps, out, ldw, col0, (hipStream_t)stream);
 }
 
-extern "C" int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream) {
+// dm_conv2d_nhwc and its variants: s2_pad0 (dm_conv2d_nhwc_s2pad0), GroupNorm(gn_G) statistics of the stored output
+// from the epilogue into gn_part (dm_debug_conv2d_gn)
+static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, void* stream) {
   dm::refresh_toggles();
   if (!d || !d->x || !d->w || !d->y) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   dm::ConvArgs a{};
+  a.s2_pad0 = s2_pad0;
+  a.gn_part = gn_part;
+  a.gn_G = gn_G;
   a.x1 = d->x; a.x1_pitch = d->x_pitch; a.Cin1 = d->Cin; a.Hin = d->Hin; a.Win = d->Win;
   a.taps = d->taps; a.stride = d->stride; a.upsample = d->upsample;
   a.x2 = d->x2; a.x2_pitch = d->x2_pitch; a.Cin2 = d->Cin2;
@@ -251,6 +256,24 @@ extern "C" int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream) {
     a.wino_fold = d->w_wino_fold;
   }
   return dm::conv2d_igemm(a, (hipStream_t)stream);
+}
+
+extern "C" int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream) { return conv2d_from_desc(d, 0, nullptr, 0, stream); }
+
+extern "C" int dm_conv2d_nhwc_s2pad0(const dm_conv_desc* d, void* stream) {
+  if (d && !(d->taps == 9 && d->stride == 2 && d->upsample == 0)) {
+    dm::set_error("dm_conv2d_nhwc_s2pad0: the bottom/right-padded form is for 3x3 stride-2 convs");
+    return DM_ERR_ARG;
+  }
+  return conv2d_from_desc(d, 1, nullptr, 0, stream);
+}
+
+// Operator tests of the producer epilogues' GroupNorm statistics: the conv of `d` (s2_pad0 as above) with the
+// statistics of its stored output for GroupNorm(G) written to part ([B][ceil(Hout Wout / 64)][G] {sum, sum of
+// squares}, the layout dm_groupnorm_affine leaves in its scratch). Fails where the chosen kernel cannot emit them.
+extern "C" int dm_debug_conv2d_gn(const dm_conv_desc* d, int s2_pad0, int G, void* part, void* stream) {
+  if (!part || G <= 0 || (s2_pad0 != 0 && s2_pad0 != 1)) { dm::set_error("dm_debug_conv2d_gn: arguments"); return DM_ERR_ARG; }
+  return conv2d_from_desc(d, s2_pad0, (double2*)part, G, stream);
 }
 
 extern "C" int64_t dm_conv_weight_wino_bytes(int Cout, int Cin, int Cin2) {

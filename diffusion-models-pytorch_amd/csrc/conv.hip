@@ -3,6 +3,8 @@
 // Replaces the torch.nn.Conv2d calls of the reference denoisers:
 //   3x3 stride 1 pad 1   models/unet.py:16,26,72,118
 //   3x3 stride 2 pad 1   models/modules.py:72      (Downsample)
+//   3x3 stride 2 over an input padded at the bottom / right only (ConvArgs::s2_pad0)
+//                        models/stablediffusion/autoencoder.py:47-66 (the KL encoder's Downsample)
 //   nearest-2x + 3x3     models/modules.py:62-65   (Upsample; the 2x image is
 //                                                   never materialised)
 //   1x1                  models/unet.py:28 (shortcut), modules.py:83-86
@@ -105,8 +107,8 @@ conv_igemm_kernel(ConvArgs a) {
         iy = uy >> 1;
         ix = ux >> 1;
       } else if (MODE == CM_3X3_S2) {
-        iy = 2 * r_oy[i] + ky - 1;
-        ix = 2 * r_ox[i] + kx - 1;
+        iy = 2 * r_oy[i] + ky - 1 + a.s2_pad0;
+        ix = 2 * r_ox[i] + kx - 1 + a.s2_pad0;
         ok = ok && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
       } else {
         iy = r_oy[i] + ky - 1;
@@ -270,6 +272,10 @@ int conv2d_igemm(const ConvArgs& a, hipStream_t st) {
   DM_REQUIRE(a.Cout > 0 && a.B > 0 && a.Hin > 0 && a.Win > 0, "conv: empty problem");
   if (a.upsample) {
     DM_REQUIRE(a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win, "conv: upsample output size");
+  } else if (a.s2_pad0) {  // input padded (0, 1, 0, 1): floor((H + 1 - 3) / 2) + 1 output rows
+    DM_REQUIRE(a.s2_pad0 == 1 && a.taps == 9 && a.stride == 2, "conv: s2_pad0 is for 3x3 stride-2 convs");
+    DM_REQUIRE(a.Hin >= 2 && a.Win >= 2 && a.Hout == (a.Hin - 2) / 2 + 1 && a.Wout == (a.Win - 2) / 2 + 1,
+               "conv: 3x3 stride-2 (bottom/right padding) output size");
   } else if (a.taps == 9) {
     DM_REQUIRE(a.Hout == (a.Hin - 1) / a.stride + 1 && a.Wout == (a.Win - 1) / a.stride + 1,
                "conv: 3x3 output size");
@@ -278,7 +284,7 @@ int conv2d_igemm(const ConvArgs& a, hipStream_t st) {
   }
   const long M = (long)a.B * a.Hout * a.Wout;
   DM_REQUIRE(M > 0 && M < (1L << 31), "conv: M out of range");
-  DM_REQUIRE(a.tile >= 0 && a.tile <= 21, "conv: tile must be 0..21");
+  DM_REQUIRE(a.tile >= 0 && a.tile <= 22, "conv: tile must be 0..22");
   if (a.tile == 21 || (a.tile == 0 && a.wino_ws)) {  // the Winograd F(2,3) kernel (conv_wino.hip)
     if (conv_wino_ok(a)) {
       if (!a.gn_part || conv_can_emit_gn(a)) return conv2d_wino(a, st);
@@ -332,6 +338,7 @@ int conv_pick(const ConvArgs& a) {
   if (a.tile == 18 && conv_k32_variant_ok(a, 9)) return 5;  // forced K32 stride-2 tiles
   if (a.tile == 19 && conv_k32_variant_ok(a, 10)) return 3;  // forced K32 2-D tiles of wide maps
   if (a.tile == 20 && conv_k32_variant_ok(a, 11)) return 3;  // forced K32 64-row single-image tiles (8^2)
+  if (a.tile == 22 && conv_k32_variant_ok(a, 13)) return 5;  // forced K32 stride-2 row-segment tiles (Wout > 64)
   if (conv_pw_ok(a)) {  // split 1x1: 128x128 tiles when they still give >= 2 blocks per CU, else 128x64
     const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
     return (a.Cout >= 128 && ((M + 127) / 128) * ((a.Cout + 127) / 128) >= 512) ? 3 : 4;
@@ -358,7 +365,8 @@ bool conv_can_emit_gn(const ConvArgs& a) {
   if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a))  // StagedEpilogue over 64-pixel chunks of one image
     return a.gn_G > 0 && a.Cout % a.gn_G == 0 && (a.Cout / a.gn_G) % 4 == 0 && a.Cout / a.gn_G <= 32;
   // the K32 stride-2 tiles: a block's 64 rows are one 64-pixel chunk (two 32-row waves per column slice)
-  if (a.stride == 2 && conv_k32_pick(a) == 9)
+  // (13: the row-segment form, 64 consecutive pixels of one output row)
+  if (a.stride == 2 && (conv_k32_pick(a) == 9 || conv_k32_pick(a) == 13))
     return (a.Hout * a.Wout) % 64 == 0 && a.gn_G > 0 && a.Cout % a.gn_G == 0 && 32 % (a.Cout / a.gn_G) == 0;
   // the K32 2-D tiles of wide maps: each wave's 64 rows are one tile's 64 pixels (a disjoint cover of the image;
   // of one parity's low-res pixels for the sub-pixel upsample)

@@ -146,9 +146,11 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const int rem = p - img * PHW;
     const int pr = rem / g.PW, pc = rem - (rem / g.PW) * g.PW;
     const int b = b0 + img;
-    // S2: patch row pr = input row 2 y0 - 1 + pr; patch column pc = parity-split input column
+    // S2: patch row pr = input row 2 y0 - 1 + pr; patch column pc = parity-split input column of the tile's
+    // 2 TW + 2 from 2 x0 - 1 (x0 > 0: row-segment tiles); s2_pad0 moves both origins to 2 y0 / 2 x0
     const int u2 = pc <= g.TW ? 2 * pc : 2 * (pc - g.TW - 1) + 1;
-    const int iy = S2 ? 2 * y0 - 1 + pr : y0 - 1 + pr, ix = S2 ? u2 - 1 : x0 + pc - 1;
+    const int s2o = S2 ? a.s2_pad0 - 1 : 0;
+    const int iy = S2 ? 2 * y0 + s2o + pr : y0 - 1 + pr, ix = S2 ? 2 * x0 + u2 + s2o : x0 + pc - 1;
     const bool ok = p < g.P && b < a.B && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
     pok[j] = ok;
     const int bc = min(b, a.B - 1);
@@ -915,7 +917,8 @@ extern "C" int dm_debug_k32_stamps(void* host, int nblocks) {
 // kernel (64 x 64 tiles of four 4 x 4 images, K split in two inside the block; the plan's ksplit = 2),
 // 7 = 512-thread 128 x 128 tiles of 64 x 32 wave tiles (wide maps), 8 = variant 1 / its sub-pixel form with a
 // 32 KB GroupNorm table (inputs of up to 2048 channels at two images per tile; one block per CU), 9 = the
-// stride-2 downsample (64 x 128 tiles of 8 waves of 32 x 32 over whole output rows, one block per CU).
+// stride-2 downsample (64 x 128 tiles of 8 waves of 32 x 32 over whole output rows, one block per CU),
+// 13 = variant 9's kernel over 64-pixel segments of one output row wider than 64 pixels (s2seg_geom).
 static bool conv_k32s_ok(const ConvArgs& a) {
   if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && a.upsample == 0)) return false;
   if (a.ksplit != 2 || a.Hout * a.Wout != 16 || a.Hin != a.Hout || a.Win != a.Wout) return false;
@@ -932,6 +935,20 @@ static bool conv_k32s_ok(const ConvArgs& a) {
 }
 
 static bool t2d_geom(const ConvArgs& a, PatchGeom& g);
+
+// variant 13's geometry: one output row x 64 consecutive columns per 64-row tile (Wout > 64), a patch of 3 input
+// rows x 2 (64 + 1) parity-split columns from input column 2 x0 - 1 (2 x0 with s2_pad0): 390 pixels
+static bool s2seg_geom(const ConvArgs& a, PatchGeom& g) {
+  if (a.taps != 9 || a.stride != 2 || a.upsample || a.Cin2) return false;
+  if (a.Hin != 2 * a.Hout || a.Win != 2 * a.Wout || a.Wout <= 64 || a.Wout % 64 != 0) return false;
+  g.TB = 1;
+  g.TH = 1;
+  g.TW = 64;
+  g.PH = 3;
+  g.PW = 2 * (64 + 1);
+  g.P = g.PH * g.PW;
+  return true;
+}
 
 int conv_k32_variant_ok(const ConvArgs& a, int v) {
   if (v == 6 || v == 12) return conv_k32s_ok(a) ? 1 : 0;
@@ -955,12 +972,12 @@ int conv_k32_variant_ok(const ConvArgs& a, int v) {
     if (a.gin_part && a.gin_G > kStats) return 0;
     return staged_epilogue_ok(a) ? 1 : 0;
   }
-  if (v == 9) {
+  if (v == 9 || v == 13) {
     if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 2 && a.upsample == 0)) return 0;
     if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 != 0 || a.ksplit > 1 || a.K != 9 * a.Cin1) return 0;
     if (a.Wout % 8 != 0) return 0;
     PatchGeom g;
-    if (!conv_patch_geom(a, 64, g) || g.P > kMaxPW || g.TB > 2) return 0;
+    if (!(v == 13 ? s2seg_geom(a, g) : conv_patch_geom(a, 64, g)) || g.P > kMaxPW || g.TB > 2) return 0;
     if (a.pro_scale && 2 * g.TB * a.Cin1 > kTab) return 0;
     if (a.gin_part && g.TB * a.gin_G > kStats) return 0;
     return staged_epilogue_ok(a) ? 1 : 0;
@@ -1029,10 +1046,14 @@ static bool t2d_geom(const ConvArgs& a, PatchGeom& g) {
 
 int conv_k32_pick(const ConvArgs& a) {
   if (a.tile >= 10 && a.tile <= 20) return conv_k32_variant_ok(a, a.tile - 9) ? a.tile - 9 : 0;
+  if (a.tile == 22) return conv_k32_variant_ok(a, 13) ? 13 : 0;
   if (a.tile != 0) return 0;
   if (a.stride == 2) {  // at least one block per CU (the nominal batch keeps the choice batch-invariant)
     const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
-    return toggles().k32_s2 && conv_k32_variant_ok(a, 9) && (M / 64) * ((a.Cout + 127) / 128) >= 256 ? 9 : 0;
+    if (toggles().k32_s2 && conv_k32_variant_ok(a, 9) && (M / 64) * ((a.Cout + 127) / 128) >= 256) return 9;
+    // outputs wider than 64 pixels: row segments, for the bottom/right-padded form only (the symmetric wide
+    // downsamples keep the im2col kernel). A shape-only choice: batch-invariant.
+    return a.s2_pad0 && toggles().k32_s2 && conv_k32_variant_ok(a, 13) ? 13 : 0;
   }
   // split-K convs of maps of <= 16 pixels: 64 x 128 tiles (4x4 maps at B = 256, K split 2: 32.5 us vs
   // 34.2 us for 64 x 64 and for conv_patch3's 64 x 64 split tiles)
@@ -1072,7 +1093,7 @@ std::string conv_k32_label(const ConvArgs& a, int v) {
   if (v == 8)
     return std::string("conv_k32_kernel<128,128,64,64,") + (a.pro_scale ? "true," : "false,") + "false," +
            (a.upsample == 2 ? "true,256,208,8192>" : "false,256,208,8192>");
-  if (v == 9)
+  if (v == 9 || v == 13)
     return std::string("conv_k32_kernel<64,128,32,32,") + (a.pro_scale ? "true," : "false,") + "false,false,512,392,2048,true>";
   if (v == 11) return std::string("conv_k32_kernel<64,128,32,64,") + (a.pro_scale ? "true," : "false,") + "false,false>";
   if (v == 10)
@@ -1111,7 +1132,7 @@ static void launch_k32(const ConvArgs& a, const PatchGeom& g, hipStream_t st) {
 }
 
 int conv2d_k32(const ConvArgs& a, int v, hipStream_t st) {
-  DM_REQUIRE(v >= 1 && v <= 12 && conv_k32_variant_ok(a, v), "conv: shape not supported by the K = 32 split kernel");
+  DM_REQUIRE(v >= 1 && v <= 13 && conv_k32_variant_ok(a, v), "conv: shape not supported by the K = 32 split kernel");
   PatchGeom g;
   if (v == 6 || v == 12) {  // the small-map kernel: 8 waves (6), or its 4-wave form (12, one wave per SIMD)
     conv_patch_geom(a, 64, g);
@@ -1135,9 +1156,12 @@ int conv2d_k32(const ConvArgs& a, int v, hipStream_t st) {
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  conv_patch_geom(a, (v >= 3 && v <= 6) || v == 9 || v == 11 ? 64 : BM_K32, g);
+  if (v == 13) s2seg_geom(a, g);
+  else conv_patch_geom(a, (v >= 3 && v <= 6) || v == 9 || v == 11 ? 64 : BM_K32, g);
+  if (v == 13) note_launch("conv_k32_kernel<64,128,32,32,...,true> (stride-2 row segments)");
   switch (v) {
     case 11: launch_k32<64, 128, 32, 64, false>(a, g, st); break;
+    case 13:  // variant 9's instantiation over s2seg_geom's tiles
     case 9: launch_k32<64, 128, 32, 32, false, 512, kMaxPW, kTab, true>(a, g, st); break;
     case 8: launch_k32<128, 128, 64, 64, false, 256, kMaxP, kTabBig>(a, g, st); break;
     case 7: launch_k32<128, 128, 64, 32, false, 512, kMaxPW>(a, g, st); break;

@@ -235,7 +235,7 @@ conv_patch3_kernel(ConvArgs a, PatchGeom g) {
   const float* psrc[PJ];
   bool pok[PJ];
   int pimg[PJ];
-  const int iy_base = UP ? (y0 >> 1) - 1 : S2 ? 2 * y0 - 1 : y0 - 1;
+  const int iy_base = UP ? (y0 >> 1) - 1 : S2 ? 2 * y0 - 1 + a.s2_pad0 : y0 - 1;
 #pragma unroll
   for (int j = 0; j < PJ; ++j) {
     if constexpr (PW1) {
@@ -254,7 +254,7 @@ conv_patch3_kernel(ConvArgs a, PatchGeom g) {
     const int b = b0 + img;
     const int half = g.PW >> 1;
     const int col = S2 ? 2 * (pc - (pc >= half ? half : 0)) + (pc >= half ? 1 : 0) : pc;  // input column + 1
-    const int iy = iy_base + pr, ix = x0 + col - 1;
+    const int iy = iy_base + pr, ix = x0 + col - 1 + (S2 ? a.s2_pad0 : 0);
     const bool ok = p < g.P && b < a.B && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
     pok[j] = ok;
     const int bc = min(b, a.B - 1);

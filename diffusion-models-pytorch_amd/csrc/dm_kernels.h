@@ -138,6 +138,7 @@ struct ConvArgs {
   // the K32 variant the plan resolved at build time (conv_k32_pick + 1; 0: pick at launch), so the launch and the
   // op's profile label come from one decision
   int k32_resolved;
+  int s2_pad0;  // 1: stride-2 taps start at 2o (input padded bottom/right only); 0: at 2o - 1 (padding 1)
 };
 
 // Patch-pixel capacity of the halo-patch kernels' LDS images (fp32 / split-bf16; 128- / 64-row tiles)

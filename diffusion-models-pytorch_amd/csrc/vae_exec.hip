@@ -11,6 +11,8 @@
 // ResnetBlock's nin_shortcut is the second K segment of its conv2 (bias b2 + bs); q, k, v -> one [3C][C] weight;
 // upsample convs also in the sub-pixel form. The plan (per (B, H, W) and arithmetic) runs over five activation
 // buffers sized to the largest tensor of the network, reused by every level (a level's tensors die at its upsample).
+// The ResnetBlock / attention weights and plan builders and the arithmetic state are vae_blocks.h's, shared with the
+// encoder (vae_enc_exec.hip).
 #include <algorithm>
 #include <cmath>
 #include <functional>
@@ -22,6 +24,7 @@
 #include "dm_kernels.h"
 #include "plan.h"
 #include "exec_pack.h"
+#include "vae_blocks.h"
 
 namespace dm {
 
@@ -57,22 +60,10 @@ __global__ void vae_latent_in_kernel(const float* __restrict__ z, int ZC, long H
   }
 }
 
-struct GnW { size_t g, b; };
-struct ConvW {
-  size_t w = 0, bias = 0;
-  int Cout = 0, Cin = 0, K = 0;
-  size_t w_sub = 0;  // sub-pixel weights [4][Cout][4 Cin] of an upsample conv
-};
-struct ResW {
-  int cin, cout;
-  GnW gn1, gn2;
-  ConvW conv1, conv2;  // conv2 carries nin_shortcut as its second K segment when cin != cout
-};
-struct AttnW {
-  int C;
-  GnW gn;
-  size_t wqkv, bqkv, wproj, bproj;
-};
+using vaeb::AttnW;
+using vaeb::ConvW;
+using vaeb::GnW;
+using vaeb::ResW;
 struct LevelW {
   std::vector<ResW> blocks;
   bool has_up = false;
@@ -81,10 +72,8 @@ struct LevelW {
 
 }  // namespace
 
-struct VaeDecoder {
+struct VaeDecoder : vaeb::VaeNet {
   dm_vae_arch arch;
-  float* arena = nullptr;
-  size_t arena_floats = 0;
   size_t pq_w = 0, pq_b = 0;  // post_quant_conv [zc][zc], [zc]
   size_t in_w = 0, in_b = 0;  // conv_in, torch layout [C][zc][3][3]
   ResW mid1, mid2;
@@ -102,30 +91,12 @@ struct VaeDecoder {
   };
   PlanCache<Plan> plans;
   float* out_packed = nullptr;  // conv_out weights as [9][C][CO] (small_out_pack)
-  // arithmetic and the fp16 range fallback: as UNetModel (unet_exec.hip)
-  int base_math = conv_math_from_env();
-  int conv_math = base_math;
-  bool range_check = toggles().range_check;
-  int* range_flag = nullptr;
-  int* range_flag_host = nullptr;
-  long range_fallbacks = 0;
-  std::map<std::pair<const float*, int>, void*> split_w;
-  std::map<std::pair<const float*, int>, void*> wino_w;
-  size_t split_bytes = 0;
-  std::map<const float*, int> w_exp;
-
-  float* P(size_t off) const { return arena + off; }
+  // (the weight arena, the arithmetic and the fp16 range fallback: vaeb::VaeNet)
   ~VaeDecoder() {
     plans.clear();
     if (out_packed) (void)hipFree(out_packed);
-    for (auto& kv : split_w) (void)hipFree(kv.second);
-    for (auto& kv : wino_w) (void)hipFree(kv.second);
-    if (range_flag) (void)hipFree(range_flag);
-    if (range_flag_host) (void)hipHostFree(range_flag_host);
-    if (arena) (void)hipFree(arena);
+    free_net();
   }
-  void split_for(ConvArgs& c);
-  void split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act);
   int build_plan(Plan& pl, int B, int H, int W);
   int get_plan(int B, int H, int W, int math, Plan** out) {
     conv_math = math;
@@ -133,74 +104,6 @@ struct VaeDecoder {
                      [&](Plan& p) { return build_plan(p, B, H, W); }, out);
   }
 };
-
-// The split copy (and, for the shapes conv_wino takes, the Winograd weights) of a conv's packed weights, as
-// UNetModel::split_for; none: the conv stays on the fp32 kernels.
-void VaeDecoder::split_for(ConvArgs& c) {
-  c.ws = nullptr;
-  c.ws_np = 0;
-  c.ws_rowscale = nullptr;
-  c.range_flag = nullptr;
-  c.wino_ws = nullptr;
-  c.wino_rowscale = nullptr;
-  if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)))) return;
-  if (c.taps == 1 && conv_math != 2) return;  // the split 1x1 path is fp16x2 only
-  const int nmat = c.upsample == 2 ? 4 : 1;
-  const int ntap = c.upsample == 2 ? 4 : c.taps;
-  const auto key = std::make_pair(c.w, conv_math);
-  auto it = split_w.find(key);
-  void* p = nullptr;
-  if (it != split_w.end()) {
-    p = it->second;
-  } else {
-    const size_t nb = split_conv_weights_bytes(nmat, c.Cout, c.K, conv_math);
-    if (hipMalloc(&p, nb) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    if (split_conv_weights(c.w, nmat, c.Cout, c.K, c.Cin1, ntap, conv_math, p, nullptr) != DM_OK ||
-        hipDeviceSynchronize() != hipSuccess) {
-      (void)hipFree(p);
-      return;
-    }
-    split_w[key] = p;
-    split_bytes += nb;
-  }
-  c.ws = p;
-  c.ws_np = conv_math;
-  if (conv_math == 2) {
-    c.ws_rowscale = split_conv_rowscale(p, nmat, c.Cout, c.K);
-    c.range_flag = range_flag;
-  }
-  if (conv_math != 2 || !toggles().wino || !conv_wino_shape_ok(c)) return;
-  if (c.Wout == 4) return;  // (4-pixel-wide maps: the Winograd kernel there is a split-K form the UNet plans tune)
-  const int fold = c.Cin2 && (c.pro_scale || c.gin_part) && !c.pro_nosilu ? 1 : 0;
-  auto iw = wino_w.find(std::make_pair(c.w, fold));
-  void* wp = nullptr;
-  if (iw != wino_w.end()) {
-    wp = iw->second;
-  } else {
-    const size_t nb = wino_weights_bytes(c.Cout, c.Cin1, c.Cin2);
-    if (hipMalloc(&wp, nb) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    if (wino_weights(c.w, c.Cout, c.Cin1, c.Cin2, fold, wp, nullptr) != DM_OK) {
-      (void)hipFree(wp);
-      return;
-    }
-    wino_w[std::make_pair(c.w, fold)] = wp;
-    split_bytes += nb;
-  }
-  c.wino_ws = wp;
-  c.wino_rowscale = wino_rowscale(wp, c.Cout, c.Cin1, c.Cin2);
-  c.wino_fold = fold;
-}
-
-// fp16x2 attention GEMMs: operand exponents (exec_pack.h split_gemm_args)
-void VaeDecoder::split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act) {
-  split_gemm_args(g, conv_math, w_exp, range_flag, ea, weight, weight_n, eb_act);
-}
 
 static int vae_validate(const dm_vae_arch* a) {
   DM_REQUIRE(a != nullptr, "arch is null");
@@ -254,60 +157,12 @@ static int vae_create(const dm_vae_arch* arch, const float* const* params, const
   const int ctop = a.ch * a.ch_mult[L - 1];
   m->c_top = ctop;
 
-  auto gn = [&](int C, const char* what) {
-    GnW g;
-    g.g = pk.raw(rd.take(C, what), C);
-    g.b = pk.raw(rd.take(C, what), C);
-    return g;
-  };
-  auto resblock = [&](int cin, int cout) {
-    ResW r;
-    r.cin = cin;
-    r.cout = cout;
-    r.gn1 = gn(cin, "ResnetBlock.norm1");
-    const float* w1 = rd.take((int64_t)cout * cin * 9, "ResnetBlock.conv1.weight");
-    const float* b1 = rd.take(cout, "ResnetBlock.conv1.bias");
-    r.conv1.Cout = cout; r.conv1.Cin = cin; r.conv1.K = 9 * cin;
-    r.conv1.w = pk.reserve((int64_t)cout * 9 * cin);
-    pk.conv_at(w1, cout, cin, 9, 9 * cin, 0, r.conv1.w);
-    r.conv1.bias = pk.raw(b1, cout);
-    r.gn2 = gn(cout, "ResnetBlock.norm2");
-    const float* w2 = rd.take((int64_t)cout * cout * 9, "ResnetBlock.conv2.weight");
-    const float* b2 = rd.take(cout, "ResnetBlock.conv2.bias");
-    const int K2 = 9 * cout + (cin != cout ? cin : 0);
-    r.conv2.Cout = cout; r.conv2.Cin = cout; r.conv2.K = K2;
-    r.conv2.w = pk.reserve((int64_t)cout * K2);
-    pk.conv_at(w2, cout, cout, 9, K2, 0, r.conv2.w);
-    if (cin != cout) {
-      const float* ws = rd.take((int64_t)cout * cin, "ResnetBlock.nin_shortcut.weight");
-      const float* bs = rd.take(cout, "ResnetBlock.nin_shortcut.bias");
-      pk.conv_at(ws, cout, cin, 1, K2, 9 * cout, r.conv2.w);
-      r.conv2.bias = pk.reserve(cout);
-      pk.add_at(b2, bs, cout, r.conv2.bias);
-    } else {
-      r.conv2.bias = pk.raw(b2, cout);
-    }
-    return r;
-  };
-
+  vaeb::BlockReader br{rd, pk};
   m->in_w = pk.raw(rd.take((int64_t)ctop * zc * 9, "conv_in.weight"), (int64_t)ctop * zc * 9);
   m->in_b = pk.raw(rd.take(ctop, "conv_in.bias"), ctop);
-  m->mid1 = resblock(ctop, ctop);
-  {
-    AttnW& p = m->attn;
-    const int C = ctop;
-    p.C = C;
-    p.gn = gn(C, "AttnBlock.norm");
-    p.wqkv = pk.reserve((int64_t)3 * C * C);
-    p.bqkv = pk.reserve(3 * C);
-    for (int i = 0; i < 3; ++i) {
-      pk.raw_at(rd.take((int64_t)C * C, "AttnBlock.{q,k,v}.weight"), (int64_t)C * C, p.wqkv + (size_t)i * C * C);
-      pk.raw_at(rd.take(C, "AttnBlock.{q,k,v}.bias"), C, p.bqkv + (size_t)i * C);
-    }
-    p.wproj = pk.raw(rd.take((int64_t)C * C, "AttnBlock.proj_out.weight"), (int64_t)C * C);
-    p.bproj = pk.raw(rd.take(C, "AttnBlock.proj_out.bias"), C);
-  }
-  m->mid2 = resblock(ctop, ctop);
+  m->mid1 = br.resblock(ctop, ctop);
+  m->attn = br.attn(ctop);
+  m->mid2 = br.resblock(ctop, ctop);
   // decoder.up.{i}: registered from i = 0 (the highest resolution), run from i = L - 1; level i's first block
   // takes the channels of level i + 1 (autoencoder.py:422-440)
   m->levels.resize(L);
@@ -315,7 +170,7 @@ static int vae_create(const dm_vae_arch* arch, const float* const* params, const
     const int cout = a.ch * a.ch_mult[i];
     int cin = i == L - 1 ? ctop : a.ch * a.ch_mult[i + 1];
     for (int j = 0; j < a.num_res_blocks + 1; ++j) {
-      m->levels[i].blocks.push_back(resblock(cin, cout));
+      m->levels[i].blocks.push_back(br.resblock(cin, cout));
       cin = cout;
     }
     if (i != 0) {
@@ -332,7 +187,7 @@ static int vae_create(const dm_vae_arch* arch, const float* const* params, const
   }
   const int c0 = a.ch * a.ch_mult[0];
   m->c_out = c0;
-  m->out_gn = gn(c0, "norm_out");
+  m->out_gn = br.gn(c0, "norm_out");
   m->out_w = pk.raw(rd.take((int64_t)a.out_channels * c0 * 9, "conv_out.weight"), (int64_t)a.out_channels * c0 * 9);
   m->out_b = pk.raw(rd.take(a.out_channels, "conv_out.bias"), a.out_channels);
   if (a.post_quant) {
@@ -364,11 +219,7 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
   pl.H = H;
   pl.W = W;
   pl.math = conv_math;
-  if (!range_flag) {
-    DM_CHECK_HIP(hipMalloc(&range_flag, sizeof(int)));
-    DM_CHECK_HIP(hipMemset(range_flag, 0, sizeof(int)));
-    DM_CHECK_HIP(hipHostMalloc(&range_flag_host, sizeof(int)));
-  }
+  if (const int rcf = ensure_range_flag()) return rcf;
   const int G = arch.norm_groups, zc = arch.z_channels, L = arch.n_levels, oc = arch.out_channels;
   const float eps = arch.norm_eps;
   const int Hout = H << (L - 1), Wout = W << (L - 1);
@@ -392,115 +243,19 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
     max_chunks = std::max(max_chunks, gn_num_chunks((int)hw));
     max_c = std::max(max_c, std::max(cin, cout));
   }
-  float* bufs[3];
-  for (auto& b : bufs) b = pl.alloc((size_t)B * max_t * 4);
-  float* hbuf = pl.alloc((size_t)B * max_t * 4);   // conv1 output of a ResnetBlock
-  float* abuf = pl.alloc((size_t)B * max_t * 4);   // GroupNorm + SiLU output where a conv has no fused prologue
-  double2* part = (double2*)pl.alloc((size_t)B * max_chunks * G * sizeof(double2));
-  double2* emit_parts[2];  // producer-emitted statistics alternate between two buffers (x's and y's)
-  for (auto& e : emit_parts) e = (double2*)pl.alloc((size_t)B * max_chunks * G * sizeof(double2));
-  float* gsc = pl.alloc((size_t)B * max_c * 4);
-  float* gsh = pl.alloc((size_t)B * max_c * 4);
-  // attention scratch: qkv rows, O rows, and the scores of `sb` images at a time (bounded score scratch)
-  const int hw0 = H * W, Ca = attn.C;
-  const size_t kScoreBudget = (size_t)256 << 20;
-  const int sb = (int)std::max<size_t>(1, std::min<size_t>((size_t)B, kScoreBudget / ((size_t)hw0 * hw0 * 4)));
-  float* qkv = pl.alloc((size_t)B * hw0 * 3 * Ca * 4);
-  float* Ob = pl.alloc((size_t)B * hw0 * Ca * 4);
-  float* Sb = pl.alloc((size_t)sb * hw0 * hw0 * 4);
-
+  // the activation buffers and the block builders (vae_blocks.h)
+  vaeb::BlockPlanner bp(this, pl, B, G, eps);
+  bp.alloc(max_t, max_chunks, max_c, H * W, attn.C);
+  float* const* bufs = bp.bufs;
+  float *gsc = bp.gsc, *gsh = bp.gsh;
   Plan* P_ = &pl;
-  VaeDecoder* self = this;
-  auto add = [&](std::string label, double flops, double bytes, std::function<int(hipStream_t)> fn) {
-    pl.add(std::move(label), flops, bytes, std::move(fn));
-  };
-  auto conv_cost = [](const ConvArgs& c, double& fl, double& by) {
-    const double M = (double)c.B * c.Hout * c.Wout;
-    fl = 2.0 * M * c.Cout * c.K;
-    by = 4.0 * ((double)c.B * c.Hin * c.Win * c.Cin1 + M * c.Cin2 + (double)c.Cout * c.K + M * c.Cout +
-                (c.res ? M * c.Cout : 0.0));
-  };
-  auto gemm_cost = [](const GemmArgs& g, double& fl, double& by) {
-    const double Z = (double)g.Z1 * g.Z2;
-    fl = 2.0 * Z * g.M * g.N * g.K;
-    by = 4.0 * Z * ((double)g.M * g.K + (double)g.N * g.K + (double)g.M * g.N) + (g.res ? 4.0 * g.M * g.N : 0.0);
-  };
-  auto add_conv = [&](ConvArgs c) {
-    split_for(c);
-    c.k32_resolved = 1 + conv_k32_pick(c);
-    double fl, by;
-    conv_cost(c, fl, by);
-    add(conv_label(c), fl, by, [=](hipStream_t st) { return conv2d_igemm(c, st); });
-  };
-  auto add_gemm = [&](const GemmArgs& g) {
-    double fl, by;
-    gemm_cost(g, fl, by);
-    add(gemm_label(g), fl, by, [=](hipStream_t st) { return gemm_batched(g, st); });
-  };
-
-  // GroupNorm statistics a producer's epilogue emitted for a view (pointer -> partials)
-  struct Ready { const double2* p; int C; };
-  std::map<const float*, Ready> gn_ready;
-  int emit_next = 0;
-  auto emit_conv = [&](ConvArgs& c, const View& v) {
-    gn_ready.erase(v.p);
-    c.gn_part = nullptr;
-    c.gn_G = 0;
-    if (!toggles().gn_fusion) return;
-    ConvArgs sk = c;
-    sk.gn_part = reinterpret_cast<double2*>(16);  // placeholder: the shape check only
-    sk.gn_G = G;
-    split_for(sk);
-    if (!conv_can_emit_gn(sk)) return;
-    c.gn_part = emit_parts[emit_next];
-    emit_next ^= 1;
-    c.gn_G = G;
-    // the buffer's previous owner (two producers ago) has been consumed; drop a stale entry that points at it
-    for (auto it = gn_ready.begin(); it != gn_ready.end();)
-      it = it->second.p == c.gn_part ? gn_ready.erase(it) : std::next(it);
-    gn_ready[v.p] = {c.gn_part, v.C};
-  };
-  auto gn_stats = [&](const View& v) -> const double2* {
-    auto it = gn_ready.find(v.p);
-    if (it != gn_ready.end() && it->second.C == v.C) return it->second.p;
-    add("gn_partial", 0, 4.0 * v.B * v.H * v.W * v.C, [=](hipStream_t st) { return gn_partial(v, G, part, st); });
-    return part;
-  };
-  // GroupNorm(G) + SiLU of v as conv c's prologue: in-kernel finalize where the conv keeps its tables in LDS and the
-  // map is small, else a gn_finalize launch (as the UNet plan's gn_prologue, at this network's eps)
-  auto gn_prologue = [&](ConvArgs& c, const View& v, const double2* stp, const GnW& gw) {
-    c.pro_scale = gsc;
-    c.pro_shift = gsh;
-    split_for(c);
-    const long imgs = c.taps == 1 ? 127 / ((long)c.Hout * c.Wout) + 2 : [&] {
-      PatchGeom gg{};
-      conv_patch_pick(c, gg);
-      return (long)gg.TB;
-    }();
-    const float* gamma = P(gw.g);
-    const float* beta = P(gw.b);
-    if (conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
-      c.gin_part = stp; c.gin_G = G; c.gin_nchunk = gn_num_chunks(v.H * v.W);
-      c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = eps;
-      c.gin_gamma = gamma; c.gin_beta = beta; c.gin_ms = nullptr; c.gin_mb = nullptr; c.gin_mp = 0;
-      return;
-    }
-    add("gn_finalize", 0, 8.0 * B * v.C,
-        [=](hipStream_t st) { return gn_finalize(v, G, stp, eps, gamma, beta, gsc, gsh, st); });
-  };
-
-  int cur_buf = 0;
-  auto next_buf = [&]() {
-    cur_buf = (cur_buf + 1) % 3;
-    return bufs[cur_buf];
-  };
 
   // --- latent entry: scale, post_quant_conv
   {
     const float* w = arch.post_quant ? P(pq_w) : nullptr;
     const float* bb = arch.post_quant ? P(pq_b) : nullptr;
     const long hw = (long)H * W, n = (long)B * hw;
-    add("vae_latent_in_kernel", 2.0 * n * zc * zc, 8.0 * n * zc, [=](hipStream_t st) {
+    pl.add("vae_latent_in_kernel", 2.0 * n * zc * zc, 8.0 * n * zc, [=](hipStream_t st) {
       hipLaunchKernelGGL(vae_latent_in_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P_->z, zc, hw, n,
                          P_->scale, w, bb, zq);
       DM_LAUNCH_CHECK();
@@ -515,144 +270,21 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
     const float* w = P(in_w) + (size_t)c0 * zc * 9;
     const float* bb = P(in_b) + c0;
     const View ys{x.p + c0, B, H, W, cn, c_top};
-    add("conv3x3_small_in", 2.0 * B * H * W * cn * 9 * zc, 4.0 * B * H * W * (zc + cn),
+    pl.add("conv3x3_small_in", 2.0 * B * H * W * cn * 9 * zc, 4.0 * B * H * W * (zc + cn),
         [=](hipStream_t st) { return conv3x3_small_in(zq, B, zc, H, W, w, bb, cn, ys, st); });
   }
 
-  auto resblock = [&](const ResW& r, const View& xin) -> View {
-    const int Ho = xin.H, Wo = xin.W;
-    View y{next_buf(), B, Ho, Wo, r.cout, r.cout};
-    View va{abuf, B, Ho, Wo, r.cin, r.cin};
-    View vh{hbuf, B, Ho, Wo, r.cout, r.cout};
-    View va2{abuf, B, Ho, Wo, r.cout, r.cout};
-    const int nchunk = gn_num_chunks(Ho * Wo);
-    ConvArgs c1{};
-    c1.x1 = xin.p; c1.x1_pitch = xin.pitch; c1.Cin1 = r.cin; c1.Hin = Ho; c1.Win = Wo;
-    c1.taps = 9; c1.stride = 1;
-    c1.w = P(r.conv1.w); c1.K = r.conv1.K;
-    c1.y = hbuf; c1.y_pitch = r.cout; c1.Cout = r.cout; c1.B = B; c1.pick_B = kPickBatch; c1.Hout = Ho; c1.Wout = Wo;
-    c1.bias = P(r.conv1.bias);
-    ConvArgs c2{};
-    c2.x1 = hbuf; c2.x1_pitch = r.cout; c2.Cin1 = r.cout; c2.Hin = Ho; c2.Win = Wo;
-    c2.taps = 9; c2.stride = 1;
-    c2.w = P(r.conv2.w); c2.K = r.conv2.K;
-    c2.y = y.p; c2.y_pitch = y.pitch; c2.Cout = r.cout; c2.B = B; c2.pick_B = kPickBatch; c2.Hout = Ho; c2.Wout = Wo;
-    c2.bias = P(r.conv2.bias);
-    if (r.cin != r.cout) {
-      c2.x2 = xin.p; c2.x2_pitch = xin.pitch; c2.Cin2 = r.cin;
-    } else {
-      c2.res = xin.p; c2.res_pitch = xin.pitch;
-    }
-    split_for(c1);
-    split_for(c2);
-    const bool fuse1 = conv_pick(c1) >= 3, fuse2 = conv_pick(c2) >= 3;
-    const double2* st1 = gn_stats(xin);
-    const GnW g1 = r.gn1, g2 = r.gn2;
-    if (fuse1) {
-      gn_prologue(c1, xin, st1, g1);
-    } else {
-      add("gn_apply", 0, 8.0 * B * Ho * Wo * r.cin, [=](hipStream_t st) {
-        return gn_apply(xin, G, st1, nchunk, eps, self->P(g1.g), self->P(g1.b), nullptr, nullptr, 0, 1, va, st);
-      });
-      c1.x1 = abuf; c1.x1_pitch = r.cin;
-    }
-    emit_conv(c1, vh);
-    add_conv(c1);
-    const double2* st2 = gn_stats(vh);
-    if (fuse2) {
-      gn_prologue(c2, vh, st2, g2);
-    } else {
-      add("gn_apply", 0, 8.0 * B * Ho * Wo * r.cout, [=](hipStream_t st) {
-        return gn_apply(vh, G, st2, nchunk, eps, self->P(g2.g), self->P(g2.b), nullptr, nullptr, 0, 1, va2, st);
-      });
-      c2.x1 = abuf;
-    }
-    emit_conv(c2, y);
-    add_conv(c2);
-    return y;
-  };
-
   // --- middle
-  x = resblock(mid1, x);
-  {
-    // mid.attn_1 (autoencoder.py:158-182): one head of C channels over L = H W tokens, scores scaled by C^-1/2.
-    // Unfused: qkv (GroupNorm folded into its A load), per image S = (s q) k^T, softmax rows, O = P v, then proj_out
-    // + residual. attn_flash / attn_fused stop at head dims 80 / L = 256 and do not take this shape.
-    const AttnW p = attn;
-    const int C = p.C, hw = hw0;
-    const View xin = x;
-    View y{next_buf(), B, H, W, C, C};
-    const double2* sta = gn_stats(xin);
-    const float sa = (float)std::pow((double)C, -0.5);
-    ConvArgs cq{};
-    cq.x1 = xin.p; cq.x1_pitch = xin.pitch; cq.Cin1 = C; cq.Hin = H; cq.Win = W; cq.taps = 1; cq.stride = 1;
-    cq.w = P(p.wqkv); cq.K = C; cq.y = qkv; cq.y_pitch = 3 * C; cq.Cout = 3 * C; cq.B = B; cq.pick_B = kPickBatch;
-    cq.Hout = H; cq.Wout = W; cq.bias = P(p.bqkv); cq.pro_scale = gsc; cq.pro_shift = gsh; cq.pro_nosilu = 1;
-    split_for(cq);
-    if (conv_pw_ok(cq)) {
-      gn_prologue(cq, xin, sta, p.gn);
-      add_conv(cq);
-    } else {
-      const GnW gw = p.gn;
-      add("gn_finalize", 0, 8.0 * B * C,
-          [=](hipStream_t st) { return gn_finalize(xin, G, sta, eps, self->P(gw.g), self->P(gw.b), gsc, gsh, st); });
-      GemmArgs gq{};
-      gq.M = B * hw; gq.N = 3 * C; gq.K = C; gq.Z1 = 1; gq.Z2 = 1; gq.pick_M = (long)kPickBatch * hw;
-      gq.A = xin.p; gq.lda = xin.pitch; gq.Bm = P(p.wqkv); gq.ldb = C; gq.C = qkv; gq.ldc = 3 * C;
-      gq.alpha = 1.f; gq.bias = P(p.bqkv);
-      gq.pro_scale = gsc; gq.pro_shift = gsh; gq.pro_rows = hw;
-      split_gemm(gq, 6, gq.Bm, (size_t)3 * C * C, 0);
-      add_gemm(gq);
-    }
-    for (int b0 = 0; b0 < B; b0 += sb) {
-      const int nb = std::min(sb, B - b0);
-      const float* q0 = qkv + (size_t)b0 * hw * 3 * C;
-      GemmArgs gs{};
-      gs.M = hw; gs.N = hw; gs.K = C; gs.Z1 = nb; gs.Z2 = 1; gs.pick_Z = kPickBatch;
-      gs.A = q0; gs.a_s1 = (long)hw * 3 * C; gs.lda = 3 * C;
-      gs.Bm = q0 + C; gs.b_s1 = (long)hw * 3 * C; gs.ldb = 3 * C;
-      gs.C = Sb; gs.c_s1 = (long)hw * hw; gs.ldc = hw;
-      gs.alpha = sa;
-      split_gemm(gs, 6, nullptr, 0, 6);
-      add_gemm(gs);
-      const long rows = (long)nb * hw;
-      add("softmax_rows", 0, 8.0 * rows * hw, [=](hipStream_t st) { return softmax_rows(Sb, rows, hw, hw, st); });
-      GemmArgs go{};
-      go.M = hw; go.N = C; go.K = hw; go.Z1 = nb; go.Z2 = 1; go.pick_Z = kPickBatch;
-      go.A = Sb; go.a_s1 = (long)hw * hw; go.lda = hw;
-      go.Bm = q0 + 2 * C; go.b_s1 = (long)hw * 3 * C; go.ldb = 3 * C; go.b_kn = 1;
-      go.C = Ob + (size_t)b0 * hw * C; go.c_s1 = (long)hw * C; go.ldc = C;
-      go.alpha = 1.f;
-      split_gemm(go, 14, nullptr, 0, 6);
-      add_gemm(go);
-    }
-    ConvArgs cp{};
-    cp.x1 = Ob; cp.x1_pitch = C; cp.Cin1 = C; cp.Hin = H; cp.Win = W; cp.taps = 1; cp.stride = 1;
-    cp.w = P(p.wproj); cp.K = C; cp.y = y.p; cp.y_pitch = y.pitch; cp.Cout = C; cp.B = B; cp.pick_B = kPickBatch;
-    cp.Hout = H; cp.Wout = W; cp.bias = P(p.bproj); cp.res = xin.p; cp.res_pitch = xin.pitch;
-    split_for(cp);
-    if (conv_pw_ok(cp)) {
-      emit_conv(cp, y);
-      add_conv(cp);
-    } else {
-      GemmArgs gp{};
-      gp.M = B * hw; gp.N = C; gp.K = C; gp.Z1 = 1; gp.Z2 = 1; gp.pick_M = (long)kPickBatch * hw;
-      gp.A = Ob; gp.lda = C; gp.Bm = P(p.wproj); gp.ldb = C; gp.C = y.p; gp.ldc = y.pitch;
-      gp.alpha = 1.f; gp.bias = P(p.bproj); gp.res = xin.p; gp.ld_res = xin.pitch;
-      split_gemm(gp, 6, gp.Bm, (size_t)C * C, 0);
-      gn_ready.erase(y.p);
-      add_gemm(gp);
-    }
-    x = y;
-  }
-  x = resblock(mid2, x);
+  x = bp.resblock(mid1, x);
+  x = bp.attn_block(attn, x);  // mid.attn_1
+  x = bp.resblock(mid2, x);
 
   // --- levels, from the lowest resolution upward
   for (int i = L - 1; i >= 0; --i) {
-    for (const ResW& r : levels[i].blocks) x = resblock(r, x);
+    for (const ResW& r : levels[i].blocks) x = bp.resblock(r, x);
     if (!levels[i].has_up) continue;
     const ConvW cv = levels[i].up;
-    View y{next_buf(), B, 2 * x.H, 2 * x.W, cv.Cout, cv.Cout};
+    View y{bp.next_buf(), B, 2 * x.H, 2 * x.W, cv.Cout, cv.Cout};
     ConvArgs c{};
     c.x1 = x.p; c.x1_pitch = x.pitch; c.Cin1 = cv.Cin; c.Hin = x.H; c.Win = x.W;
     c.taps = 9; c.stride = 1; c.upsample = 1;
@@ -667,10 +299,10 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
       if (conv_pick(s) >= 3) c = s;
     }
     if (c.upsample == 2)
-      emit_conv(c, y);
+      bp.emit_conv(c, y);
     else
-      gn_ready.erase(y.p);
-    add_conv(c);
+      bp.gn_ready.erase(y.p);
+    bp.add_conv(c);
     x = y;
   }
 
@@ -681,14 +313,15 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
     DM_REQUIRE(xin.H == Hout && xin.W == Wout && C == c_out, "decoder plan: output shape");
     const int nchunk = gn_num_chunks(Hout * Wout);
     const GnW lg = out_gn;
-    const double2* stl = gn_stats(xin);
+    const double2* stl = bp.gn_stats(xin);
+    const float *gamma = P(lg.g), *beta = P(lg.b);
     GnFin fin;
     if (toggles().gn_fusion && C <= 512 && C % G == 0 && nchunk <= 64) {
       fin.part = stl; fin.G = G; fin.nchunk = nchunk; fin.n = (double)Hout * Wout * (C / G); fin.eps = eps;
-      fin.gamma = P(lg.g); fin.beta = P(lg.b);
+      fin.gamma = gamma; fin.beta = beta;
     } else {
-      add("gn_finalize", 0, 8.0 * B * C,
-          [=](hipStream_t st) { return gn_finalize(xin, G, stl, eps, self->P(lg.g), self->P(lg.b), gsc, gsh, st); });
+      pl.add("gn_finalize", 0, 8.0 * B * C,
+          [=](hipStream_t st) { return gn_finalize(xin, G, stl, eps, gamma, beta, gsc, gsh, st); });
     }
     if (!out_packed) {
       DM_CHECK_HIP(hipMalloc(&out_packed, (size_t)9 * C * 8 * sizeof(float)));
@@ -697,7 +330,7 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
     }
     const float* lw = out_packed;
     const float* lb = P(out_b);
-    add("conv3x3_small_out", 2.0 * B * Hout * Wout * oc * 9 * C, 4.0 * B * Hout * Wout * (C + oc),
+    pl.add("conv3x3_small_out", 2.0 * B * Hout * Wout * oc * 9 * C, 4.0 * B * Hout * Wout * (C + oc),
         [=](hipStream_t st) {
           return fin.part ? conv3x3_small_out(xin, lw, lb, oc, P_->out, st, nullptr, nullptr, fin)
                           : conv3x3_small_out(xin, lw, lb, oc, P_->out, st, gsc, gsh);

@@ -71,6 +71,15 @@ class VaeArch(ctypes.Structure):
     ]
 
 
+class VaeEncArch(ctypes.Structure):
+    """dm_vae_enc_arch (include/dm_hip.h)."""
+    _fields_ = [
+        ('in_channels', ctypes.c_int), ('z_channels', ctypes.c_int), ('ch', ctypes.c_int),
+        ('n_levels', ctypes.c_int), ('ch_mult', ctypes.c_int * DM_MAX_STAGES), ('num_res_blocks', ctypes.c_int),
+        ('norm_groups', ctypes.c_int), ('norm_eps', ctypes.c_float), ('quant', ctypes.c_int),
+    ]
+
+
 class StepDesc(ctypes.Structure):
     _fields_ = [
         ('B', ctypes.c_int), ('C', ctypes.c_int), ('HW', ctypes.c_int), ('Cm', ctypes.c_int),
@@ -258,6 +267,8 @@ def _declare(L: ctypes.CDLL):
     L.dm_pack_conv_weight.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
                                       vp]
     L.dm_conv2d_nhwc.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.dm_conv2d_nhwc_s2pad0.argtypes = [ctypes.POINTER(ConvDesc), vp]
+    L.dm_debug_conv2d_gn.argtypes = [ctypes.POINTER(ConvDesc), ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_pack_conv_weight_subpixel.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_debug_launch_log.argtypes = [ctypes.c_int]
     L.dm_debug_launch_log_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
@@ -313,6 +324,23 @@ def _declare(L: ctypes.CDLL):
     L.dm_vae_decoder_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     L.dm_vae_decoder_destroy.argtypes = [vp]
     L.dm_vae_decoder_destroy.restype = None
+    L.dm_vae_encoder_param_count.argtypes = [ctypes.POINTER(VaeEncArch), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_encoder_create.argtypes = [ctypes.POINTER(VaeEncArch), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.c_int, vp, ctypes.POINTER(vp)]
+    L.dm_vae_encoder_forward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_float, vp, vp,
+                                         vp]
+    L.dm_vae_encoder_set_math.argtypes = [vp, ctypes.c_int]
+    L.dm_vae_encoder_get_math.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_encoder_range_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_encoder_profile.argtypes = [vp, ctypes.c_int]
+    L.dm_vae_encoder_profile_count.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_encoder_profile_get.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                             ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
+    L.dm_vae_encoder_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
+    L.dm_vae_encoder_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
+    L.dm_vae_encoder_destroy.argtypes = [vp]
+    L.dm_vae_encoder_destroy.restype = None
     L.dm_unet_share_workspace.argtypes = [vp, vp]
     L.dm_unet_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     L.dm_dit_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
@@ -537,16 +565,16 @@ def dit_math(handle, kind: Optional[str] = None) -> str:
     return {v: n for n, v in kinds.items()}[k.value]
 
 
-def vae_math(handle, kind: Optional[str] = None) -> str:
-    """Set (kind given) and return the arithmetic of a native VAE decoder handle: 'fp16x2' (default), 'bf16x3' or
-    'fp32' (dm_vae_decoder_set_math / dm_vae_decoder_get_math)."""
+def vae_math(handle, kind: Optional[str] = None, abi: str = 'dm_vae_decoder') -> str:
+    """Set (kind given) and return the arithmetic of a native VAE decoder (abi 'dm_vae_encoder': encoder) handle:
+    'fp16x2' (default), 'bf16x3' or 'fp32' (dm_vae_decoder_set_math / dm_vae_decoder_get_math and the encoder's)."""
     L = load()
     if kind is not None:
         if kind not in CONV_MATH:
-            raise ValueError(f'decoder math must be one of {sorted(CONV_MATH)}')
-        check(L.dm_vae_decoder_set_math(handle, CONV_MATH[kind]), 'dm_vae_decoder_set_math')
+            raise ValueError(f'{abi[7:]} math must be one of {sorted(CONV_MATH)}')
+        check(getattr(L, abi + '_set_math')(handle, CONV_MATH[kind]), abi + '_set_math')
     k = ctypes.c_int()
-    check(L.dm_vae_decoder_get_math(handle, ctypes.byref(k)), 'dm_vae_decoder_get_math')
+    check(getattr(L, abi + '_get_math')(handle, ctypes.byref(k)), abi + '_get_math')
     return {v: n for n, v in CONV_MATH.items()}[k.value]
 
 
@@ -565,6 +593,21 @@ def unet_conv_math(handle, kind: Optional[str] = None) -> str:
 
 def conv2d_nhwc(desc: ConvDesc, device=None):
     check(load().dm_conv2d_nhwc(ctypes.byref(desc), stream_handle(device)), 'dm_conv2d_nhwc')
+
+
+def conv2d_nhwc_s2pad0(desc: ConvDesc, device=None):
+    """dm_conv2d_nhwc for a 3x3 stride-2 conv whose input is padded at the bottom and right only (F.pad(x, (0, 1, 0, 1))
+    + stride 2, padding 0: the KL autoencoder's Downsample): output pixel o reads input rows / columns 2o .. 2o + 2."""
+    check(load().dm_conv2d_nhwc_s2pad0(ctypes.byref(desc), stream_handle(device)), 'dm_conv2d_nhwc_s2pad0')
+
+
+def conv2d_gn_stats(desc: ConvDesc, G: int, part: torch.Tensor, s2_pad0: bool = False, device=None):
+    """The conv of `desc` with the GroupNorm(G) statistics of its stored output written by the kernel's epilogue to
+    `part` (float64 [B, ceil(Hout Wout / 64), G, 2]: sum, sum of squares -- what groupnorm_affine leaves in its
+    scratch). Raises where the kernel the conv runs on cannot emit them (dm_debug_conv2d_gn; operator tests)."""
+    require_device_tensor(part, 'part', torch.float64)
+    check(load().dm_debug_conv2d_gn(ctypes.byref(desc), int(bool(s2_pad0)), G, part.data_ptr(), stream_handle(device)),
+          'dm_debug_conv2d_gn')
 
 
 def gemm(desc: GemmDesc, device=None):

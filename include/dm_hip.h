@@ -242,6 +242,51 @@ int dm_vae_decoder_memory(const dm_vae_decoder* dec, int64_t* weight_bytes, int6
 int dm_vae_decoder_plan_stats(const dm_vae_decoder* dec, int64_t* builds, int* cached);
 void dm_vae_decoder_destroy(dm_vae_decoder* dec);
 
+/* The image encoder of the same KL autoencoder (csrc/vae_enc_exec.hip; reference
+ * models/stablediffusion/autoencoder.py Encoder, AutoEncoderKL.encode, DiagonalGaussianDistribution): conv_in, per
+ * level num_res_blocks ResnetBlocks and (except at the last level) a 3x3 stride-2 Downsample over the input padded at
+ * the bottom and right, the middle block with one single-head attention, norm_out -> SiLU -> conv_out
+ * (2 z_channels), the optional 1x1 quant_conv, then the posterior: mean | logvar, logvar clamped to [-30, 20].
+ * Parameters in the reference's state_dict() order: `encoder.*` (conv_in; down.{i}.block.{j}: norm1, conv1, norm2,
+ * conv2[, nin_shortcut]; down.{i}.downsample.conv; mid.block_1, mid.attn_1: norm, q, k, v, proj_out, mid.block_2;
+ * norm_out; conv_out), then `quant_conv.*`; attention and quant_conv weights are [C][C] matrices. */
+typedef struct dm_vae_enc_arch {
+  int in_channels;     /* image channels (1..4) */
+  int z_channels;      /* latent channels (1..4); conv_out and quant_conv have 2 z_channels */
+  int ch;
+  int n_levels;
+  int ch_mult[DM_MAX_STAGES];
+  int num_res_blocks;  /* per level (>= 1) */
+  int norm_groups;     /* 32 */
+  float norm_eps;      /* 1e-6 */
+  int quant;           /* 1: a 1x1 quant_conv 2 z_channels -> 2 z_channels runs before the split into mean | logvar */
+} dm_vae_enc_arch;
+
+typedef struct dm_vae_encoder dm_vae_encoder;
+
+int dm_vae_encoder_param_count(const dm_vae_enc_arch* arch, int* n_params);
+int dm_vae_encoder_create(const dm_vae_enc_arch* arch, const float* const* params, const int64_t* numels, int n_params,
+                          void* stream, dm_vae_encoder** out);
+/* x: [B, in_channels, H, W] f32 NCHW images, H and W multiples of f = 2^(n_levels-1) (DM_ERR_ARG otherwise; the
+ * latent map (H / f) (W / f) must also be a multiple of 4 pixels: DM_ERR_UNSUPPORTED). noise (nullable):
+ * [B, z_channels, H / f, W / f]. z_out = scale * (mean + exp(0.5 logvar) * noise), or scale * mean without noise (the
+ * posterior's mode); `scale` is the float32 of the reference's scale_factor (models/dit: `scale_factor * z`), 1.0f
+ * for the plain latent. moments_out (nullable): [B, 2 z_channels, H / f, W / f], mean then the clamped logvar.
+ * Plans are cached per (B, H, W) and arithmetic. */
+int dm_vae_encoder_forward(dm_vae_encoder* enc, const float* x, int B, int H, int W, const float* noise, float scale,
+                           float* z_out, float* moments_out, void* stream);
+/* As the decoder's. */
+int dm_vae_encoder_set_math(dm_vae_encoder* enc, int kind);
+int dm_vae_encoder_get_math(const dm_vae_encoder* enc, int* kind);
+int dm_vae_encoder_range_stats(const dm_vae_encoder* enc, int64_t* fallbacks, int* active_math);
+int dm_vae_encoder_profile(dm_vae_encoder* enc, int enable);
+int dm_vae_encoder_profile_count(dm_vae_encoder* enc, int* n_ops);
+int dm_vae_encoder_profile_get(dm_vae_encoder* enc, int i, char* label, int label_len, double* flops, double* bytes,
+                               double* ms_total, int64_t* launches);
+int dm_vae_encoder_memory(const dm_vae_encoder* enc, int64_t* weight_bytes, int64_t* workspace_bytes);
+int dm_vae_encoder_plan_stats(const dm_vae_encoder* enc, int64_t* builds, int* cached);
+void dm_vae_encoder_destroy(dm_vae_encoder* enc);
+
 /* Sampler update -----------------------------------------------------------
  * One elementwise pass doing predict() (ddpm.py:174-203), the optional CFG
  * combine (ddim.py:185 / ddpm.py:343-345, with the second predict under
@@ -423,6 +468,12 @@ typedef struct dm_conv_desc {
 /* 1x1 convs (taps 1, K = Cin, Cin % 32 == 0) with DM_SPLIT_FP16X2 weights run on the split kernel
  * with the same prologue / epilogue options: the static-weight GEMMs of the attention blocks. */
 int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream);
+/* The same conv for a 3x3 stride-2 whose input is zero-padded at the bottom and right only (the KL autoencoder's
+ * Downsample: pad (0, 1, 0, 1), then stride 2 without padding): output pixel o reads input rows / columns
+ * 2o .. 2o + 2 instead of 2o - 1 .. 2o + 1; Hout = (Hin - 2) / 2 + 1, likewise Wout. DM_ERR_ARG unless taps == 9,
+ * stride == 2 and upsample == 0. tile as above; 18 forces the K = 32 split kernel's whole-row stride-2 tiles
+ * (Wout <= 64), 22 its 64-pixel row segments (Wout > 64, Wout % 64 == 0), which tile 0 takes for this form only. */
+int dm_conv2d_nhwc_s2pad0(const dm_conv_desc* d, void* stream);
 
 typedef struct dm_gemm_desc {
   int M, N, K, Z1, Z2;

@@ -2,6 +2,10 @@
 level; 4 x 32 x 32 latents -> 256^2 images), synthetic weights (tests/vae_ref.py recipe).
 
     python tools/vae_bench.py [--batches 8 16] [--iters 5] [--repeats 3] [--json out.json]
+    python tools/vae_bench.py --encode [--batches 16] [--image 256]
+
+--encode times the image encoder instead (dm_vae_encoder; 256^2 images -> 4 x 32 x 32 latents, the posterior's mode)
+against tests/vae_enc_ref.py's float32 torch graph on the same device, with the encoder's per-op profile.
 
 Per batch size: the native decoder (dm_vae_decoder, one plan = one hipGraph) in ms/image and img/s, the median of
 `repeats` timed windows of `iters` decodes after a warm-up decode; then, in the same process on the same device, the
@@ -22,7 +26,7 @@ import torch  # noqa: E402
 
 import dmhip  # noqa: E402
 from models.dit.autoencoder import AutoEncoderKL  # noqa: E402
-from tests import vae_ref  # noqa: E402
+from tests import vae_enc_ref, vae_ref  # noqa: E402
 
 
 def timed(fn, iters, repeats):
@@ -41,8 +45,58 @@ def timed(fn, iters, repeats):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def encode_main(args, dev):
+    """The encoder arm: img/s of encode_to_latent at each batch size, the torch-ROCm graph, the per-op profile."""
+    name = {'T1': 'E1', 'T2': 'E2', 'T3': 'E3'}[args.config]
+    sd = vae_enc_ref.full_weights(name)
+    sd_dev = {k: v.to(dev) for k, v in sd.items() if k.startswith(('encoder.', 'quant_conv.'))}
+    S = args.image
+    result = dict(config=name, image=S, mode='encode', runs=[])
+    for B in args.batches:
+        model = AutoEncoderKL.from_state_dict(vae_enc_ref.diffusers_config(name), sd, encode_batch=B)
+        x = (torch.rand((B, 3, S, S), generator=torch.Generator().manual_seed(1)) * 2 - 1).to(dev)
+        h = model.encoder_handle(dev)
+        med, lo, hi = timed(lambda: model.encode_to_latent(x), args.iters, args.repeats)
+        run = dict(B=B, native_ms=med, native_ms_min=lo, native_ms_max=hi, native_ms_per_image=med / B,
+                   native_img_per_s=B / med * 1e3)
+        print(f'native  B={B:3d} {med:9.2f} ms/encode ({lo:.2f} .. {hi:.2f})  {med / B:8.3f} ms/image  '
+              f'{B / med * 1e3:8.1f} img/s', flush=True)
+        if not args.no_torch:
+            out_t = vae_enc_ref.moments(sd_dev, x)[:, :4]
+            err = (model.encode_to_latent(x) - out_t).abs().max().item()
+            tm, tlo, thi = timed(lambda: vae_enc_ref.moments(sd_dev, x), args.iters, args.repeats)
+            run.update(torch_ms=tm, torch_ms_min=tlo, torch_ms_max=thi, torch_ms_per_image=tm / B,
+                       torch_img_per_s=B / tm * 1e3, native_vs_torch_max_abs=err)
+            print(f'torch   B={B:3d} {tm:9.2f} ms/encode ({tlo:.2f} .. {thi:.2f})  {tm / B:8.3f} ms/image  '
+                  f'{B / tm * 1e3:8.1f} img/s  (native vs torch max-abs {err:.2e})', flush=True)
+            del out_t
+        dmhip.unet_profile_enable(h, 1, 'dm_vae_encoder')
+        for _ in range(3):
+            model.encode_to_latent(x)
+        torch.cuda.synchronize()
+        ops = dmhip.unet_profile_read(h, 'dm_vae_encoder')
+        dmhip.unet_profile_enable(h, 0, 'dm_vae_encoder')
+        per_fwd = sum(o['ms_total'] for o in ops) / max(ops[0]['launches'], 1)
+        fam = {}
+        for o in ops:
+            f = fam.setdefault(o['label'], dict(ms=0.0, n=0, flops=0.0))
+            f['ms'] += o['ms_total'] / max(o['launches'], 1)
+            f['n'] += 1
+            f['flops'] += o['flops']
+        run.update(profile_ms=per_fwd, families=fam)
+        print(f'profile B={B}: {per_fwd:.2f} ms over {len(ops)} launches')
+        for k, v in sorted(fam.items(), key=lambda kv: -kv[1]['ms']):
+            tf = v['flops'] / v['ms'] / 1e9 if v['ms'] > 0 else 0.0
+            print(f'  {v["ms"]:9.3f} ms {100 * v["ms"] / per_fwd:5.1f} %  x{v["n"]:3d}  {tf:7.1f} TFLOP/s  {k}')
+        result['runs'].append(run)
+        model.close()
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--encode', action='store_true', help='time the image encoder instead of the decoder')
+    ap.add_argument('--image', type=int, default=256, help='--encode: image height and width')
     ap.add_argument('--batches', type=int, nargs='+', default=[8, 16])
     ap.add_argument('--latent', type=int, default=32)
     ap.add_argument('--iters', type=int, default=5)
@@ -55,6 +109,13 @@ def main():
         raise SystemExit('vae_bench: no ROCm GPU visible (timings are taken on the GPU only)')
     dev = torch.device('cuda', 0)
     torch.set_grad_enabled(False)
+    if args.encode:
+        result = encode_main(args, dev)
+        if args.json:
+            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+            with open(args.json, 'w') as f:
+                json.dump(result, f, indent=1)
+        return
     sd = vae_ref.weights(args.config)
     sd_dev = {k: v.to(dev) for k, v in sd.items()}
     S = args.latent
