@@ -215,7 +215,16 @@ extern "C" int dm_pack_conv_weight(const float* w, int Cout, int Cin, int taps, 
 
 // dm_conv2d_nhwc and its variants: s2_pad0 (dm_conv2d_nhwc_s2pad0), GroupNorm(gn_G) statistics of the stored output
 // from the epilogue into gn_part (dm_debug_conv2d_gn)
-static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, void* stream) {
+// (gin: dm_debug_conv2d_gin's in-kernel GroupNorm finalize of the prologue, ConvArgs::gin_*)
+struct GinHook {
+  const double2* part;
+  int G, nchunk;
+  float eps;
+  const float *gamma, *beta, *ms, *mb;
+  int mp;
+};
+static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, void* stream,
+                            const GinHook* gin = nullptr) {
   dm::refresh_toggles();
   if (!d || !d->x || !d->w || !d->y) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   dm::ConvArgs a{};
@@ -255,7 +264,30 @@ static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part
     a.wino_rowscale = dm::wino_rowscale(d->w_wino, a.Cout, a.Cin1, a.Cin2);
     a.wino_fold = d->w_wino_fold;
   }
-  return dm::conv2d_igemm(a, (hipStream_t)stream);
+  if (gin) {
+    if (a.pro_scale || !gin->part || gin->G <= 0 || a.Cin1 <= 0 || a.Cin1 % gin->G != 0 || gin->nchunk <= 0 ||
+        (gin->ms != nullptr) != (gin->mb != nullptr)) {
+      dm::set_error("dm_debug_conv2d_gin: arguments");
+      return DM_ERR_ARG;
+    }
+    // the plans leave their (then unread) table pointers in pro_scale / pro_shift: the kernels take the presence of
+    // a prologue from them and read the partials instead. Here the partials' own address stands in.
+    a.pro_scale = a.pro_shift = reinterpret_cast<const float*>(gin->part);
+    a.gin_part = gin->part; a.gin_G = gin->G; a.gin_nchunk = gin->nchunk;
+    a.gin_n = (double)a.Hin * a.Win * (a.Cin1 / gin->G);
+    a.gin_eps = gin->eps; a.gin_gamma = gin->gamma; a.gin_beta = gin->beta;
+    a.gin_ms = gin->ms; a.gin_mb = gin->mb; a.gin_mp = gin->mp;
+    if (!dm::conv_lds_tables(a)) {
+      dm::set_error("dm_debug_conv2d_gin: the conv does not stage its GroupNorm tables in LDS (conv_lds_tables)");
+      return DM_ERR_UNSUPPORTED;
+    }
+  }
+  const int rc = dm::conv2d_igemm(a, (hipStream_t)stream);
+  // dm_debug_conv2d_gn / dm_debug_conv2d_gin only (null on every other entry): conv_label(a) goes to the launch log after the
+  // launchers' own lines. It is the dispatcher's choice restated from the same ConvArgs (the label function the
+  // profiles use, which mirrors conv2d_igemm's dispatch), not a record made by the launcher.
+  if ((gn_part || gin) && rc == DM_OK) dm::note_launch(dm::conv_label(a).c_str());
+  return rc;
 }
 
 extern "C" int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream) { return conv2d_from_desc(d, 0, nullptr, 0, stream); }
@@ -271,9 +303,24 @@ extern "C" int dm_conv2d_nhwc_s2pad0(const dm_conv_desc* d, void* stream) {
 // Operator tests of the producer epilogues' GroupNorm statistics: the conv of `d` (s2_pad0 as above) with the
 // statistics of its stored output for GroupNorm(G) written to part ([B][ceil(Hout Wout / 64)][G] {sum, sum of
 // squares}, the layout dm_groupnorm_affine leaves in its scratch). Fails where the chosen kernel cannot emit them.
+// With the launch log on, the conv's kernel instantiation (conv_label) is logged after the launchers' own lines.
 extern "C" int dm_debug_conv2d_gn(const dm_conv_desc* d, int s2_pad0, int G, void* part, void* stream) {
   if (!part || G <= 0 || (s2_pad0 != 0 && s2_pad0 != 1)) { dm::set_error("dm_debug_conv2d_gn: arguments"); return DM_ERR_ARG; }
   return conv2d_from_desc(d, s2_pad0, (double2*)part, G, stream);
+}
+
+// Operator tests of the convs' in-kernel GroupNorm finalize (tests/test_gpu_norm_ops.py): the conv of `d` (pro_scale
+// null, pro_nosilu honoured) with its prologue tables built in the kernel from the chunk partials gin_part
+// [B][gin_nchunk][gin_G] of x, gin_n = Hin Win Cin / gin_G. DM_ERR_UNSUPPORTED where conv_lds_tables() is false;
+// gin_ms and gin_mb come together or not at all (the plans' AdaGN form).
+extern "C" int dm_debug_conv2d_gin(const dm_conv_desc* d, int s2_pad0, const void* gin_part, int gin_G, int gin_nchunk,
+                                   float gin_eps, const float* gin_gamma, const float* gin_beta, const float* gin_ms,
+                                   const float* gin_mb, int gin_mp, void* stream) {
+  if (s2_pad0 != 0 && s2_pad0 != 1) { dm::set_error("dm_debug_conv2d_gin: arguments"); return DM_ERR_ARG; }
+  const GinHook gin{(const double2*)gin_part, gin_G, gin_nchunk, gin_eps, gin_gamma, gin_beta, gin_ms, gin_mb, gin_mp};
+  const int rc = conv2d_from_desc(d, s2_pad0, nullptr, 0, stream, &gin);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DM_OK) { dm::set_error("sync"); return DM_ERR_HIP; }
+  return rc;
 }
 
 extern "C" int64_t dm_conv_weight_wino_bytes(int Cout, int Cin, int Cin2) {
@@ -302,7 +349,8 @@ extern "C" int dm_pack_conv_weight_subpixel(const float* w, int Cout, int Cin, f
   return dm::repack_subpixel(w, Cout, Cin, out, (hipStream_t)stream);
 }
 
-extern "C" int dm_gemm(const dm_gemm_desc* d, void* stream) {
+// dm_gemm; with gn_part (dm_debug_gemm_gn) also the GroupNorm(gn_G) statistics of the output rows, images of gn_hw rows
+static int gemm_from_desc(const dm_gemm_desc* d, double2* gn_part, int gn_G, int gn_hw, void* stream) {
   dm::refresh_toggles();
   if (!d || !d->A || !d->B || !d->C) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   dm::GemmArgs g{};
@@ -313,7 +361,19 @@ extern "C" int dm_gemm(const dm_gemm_desc* d, void* stream) {
   g.alpha = d->alpha; g.bias = d->bias; g.res = d->res; g.ld_res = d->ld_res; g.act = d->act;
   g.b_scale = d->b_scale;
   g.split = d->split; g.split_ea = d->split_ea; g.split_eb = d->split_eb; g.range_flag = d->range_flag;
+  g.gn_part = gn_part; g.gn_G = gn_G; g.gn_hw = gn_hw;
   return dm::gemm_batched(g, (hipStream_t)stream);
+}
+
+extern "C" int dm_gemm(const dm_gemm_desc* d, void* stream) { return gemm_from_desc(d, nullptr, 0, 0, stream); }
+
+// Operator tests of the GEMM epilogue's GroupNorm statistics (GemmArgs::gn_part): dm_gemm with the statistics of its
+// output for GroupNorm(G) over images of hw rows written to part [M / hw][hw / 64][G]. Synchronous.
+extern "C" int dm_debug_gemm_gn(const dm_gemm_desc* d, int G, int hw, void* part, void* stream) {
+  if (!part || G <= 0 || hw <= 0) { dm::set_error("dm_debug_gemm_gn: arguments"); return DM_ERR_ARG; }
+  const int rc = gemm_from_desc(d, (double2*)part, G, hw, stream);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DM_OK) { dm::set_error("sync"); return DM_ERR_HIP; }
+  return rc;
 }
 
 extern "C" int dm_softmax_rows(float* x, int64_t rows, int L, int ld, void* stream) {

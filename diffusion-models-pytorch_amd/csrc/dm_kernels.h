@@ -267,6 +267,10 @@ struct StepArgs {
   float* e_dout;
 };
 
+// Operator tests of the GroupNorm chain (gn_partial / gn_apply through dm_groupnorm_nhwc with the test's scratch,
+// gn_finalize and its wide form through dm_debug_gn_finalize, gn_concat_stats through dm_debug_gn_concat_stats) and of
+// conv3x3_small_in / conv3x3_small_out / resample2x (dm_debug_conv3x3_small_in, dm_debug_conv3x3_small_out,
+// dm_debug_resample2x; gn.hip, elementwise.hip): tests/test_gpu_norm_ops.py.
 int gn_num_chunks(int HW);
 int gn_partial(const View& x, int G, double2* part, hipStream_t st);
 // partials of a concat [h (Ch) | skip (Cs)] from the slices' own G-group partials (group-aligned slices)

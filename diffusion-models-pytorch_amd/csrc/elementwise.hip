@@ -673,14 +673,21 @@ int small_out_pack(const float* w, int Cout, int Cin, float* wp, hipStream_t st)
   return DM_OK;
 }
 
+// conv3x3_small_out's argument checks: what it refuses and why, or null (shared with dm_debug_conv3x3_small_out,
+// which must refuse before it packs the weights)
+static const char* small_out_refusal(const View& x, int Cout, const float* pro_scale, const GnFin& fin) {
+  if (!(Cout >= 1 && Cout <= 8)) return "last conv: Cout out of range";
+  if (fin.part && !(!pro_scale && fin.G > 0 && x.C % fin.G == 0 && x.C <= kSoMaxC && fin.nchunk > 0))
+    return "last conv: in-kernel GroupNorm finalize needs groups dividing <= 512 channels";
+  if (!(x.C % 32 == 0 && x.pitch % 4 == 0)) return "last conv: Cin must be a multiple of 32";
+  if ((reinterpret_cast<uintptr_t>(x.p) & 15) != 0) return "last conv: input must be 16-byte aligned";
+  return nullptr;
+}
+
 int conv3x3_small_out(const View& x, const float* wp, const float* bias, int Cout, float* y, hipStream_t st,
                       const float* pro_scale, const float* pro_shift, const GnFin& fin) {
-  DM_REQUIRE(Cout >= 1 && Cout <= 8, "last conv: Cout out of range");
-  DM_REQUIRE(!fin.part || (!pro_scale && fin.G > 0 && x.C % fin.G == 0 && x.C <= kSoMaxC && fin.nchunk > 0),
-             "last conv: in-kernel GroupNorm finalize needs groups dividing <= 512 channels");
-  DM_REQUIRE(x.C % 32 == 0 && x.pitch % 4 == 0, "last conv: Cin must be a multiple of 32");
+  if (const char* why = small_out_refusal(x, Cout, pro_scale, fin)) DM_REQUIRE(false, why);
   // wp: small_out_pack's [9][Cin][Cout rounded up to even]
-  DM_REQUIRE((reinterpret_cast<uintptr_t>(x.p) & 15) == 0, "last conv: input must be 16-byte aligned");
   const long tiles = (long)x.B * ceil_div(x.H, kSoTH) * ceil_div(x.W, kSoTW);
 #define DM_SO2(CO)                                                                                            \
   hipLaunchKernelGGL(conv3x3_small_out2_kernel<CO>, dim3((unsigned)tiles), dim3(256), 0, st, x.p, x.B, x.H, x.W, \
@@ -788,6 +795,78 @@ extern "C" int dm_debug_embed_add_silu(const float* temb, const int64_t* y, cons
   hipStream_t st = (hipStream_t)stream;
   if (!temb || !table || !out || B <= 0 || D <= 0) { set_error("bad embed_add_silu arguments"); return DM_ERR_ARG; }
   const int rc = embed_add_silu(temb, y, table, B, D, out, st, null_row);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+/* Test hooks (tests/test_gpu_norm_ops.py), synchronous, allocate nothing. dm_debug_conv3x3_small_in: the first conv
+ * (x NCHW [B][Cin][H][W], w torch [Cout][Cin][3][3]) into the NHWC view y of pitch y_pitch; part non-null: also the
+ * GroupNorm(G) chunk partials [B][ceil(H W / 64)][G] (an error where conv3x3_small_in_can_emit refuses).
+ * dm_debug_conv3x3_small_out: small_out_pack of w_torch [Cout][Cin][3][3] into wp_scratch (9 Cin (Cout rounded up to
+ * even) floats), then the last conv of the NHWC view x -> y NCHW [B][Cout][H][W]; prologue from the tables
+ * pro_scale / pro_shift [B][Cin], or finalized in the kernel from fin_part [B][fin_nchunk][fin_G].
+ * dm_debug_resample2x: avg-pool 2x2 (down) / nearest 2x of the NHWC view x [B][Hin][Win][C]. */
+extern "C" int dm_debug_conv3x3_small_in(const float* x, int B, int Cin, int H, int W, const float* w,
+                                         const float* bias, int Cout, float* y, int y_pitch, void* part, int G,
+                                         void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !w || !bias || !y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || y_pitch < Cout) {
+    set_error("bad conv3x3_small_in arguments");
+    return DM_ERR_ARG;
+  }
+  View vy{y, B, H, W, Cout, y_pitch};
+  const int rc = conv3x3_small_in(x, B, Cin, H, W, w, bias, Cout, vy, st, (double2*)part, part ? G : 0);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+extern "C" int dm_debug_conv3x3_small_out(const float* x, int B, int H, int W, int Cin, int pitch,
+                                          const float* w_torch, float* wp_scratch, const float* bias, int Cout,
+                                          float* y, const float* pro_scale, const float* pro_shift,
+                                          const void* fin_part, int fin_G, int fin_nchunk, float fin_eps,
+                                          const float* fin_gamma, const float* fin_beta, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !w_torch || !wp_scratch || !bias || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || pitch < Cin ||
+      (pro_scale != nullptr) != (pro_shift != nullptr)) {
+    set_error("bad conv3x3_small_out arguments");
+    return DM_ERR_ARG;
+  }
+  GnFin fin;
+  if (fin_part) {
+    fin.part = (const double2*)fin_part;
+    fin.G = fin_G;
+    fin.nchunk = fin_nchunk;
+    fin.n = fin_G > 0 ? (double)H * W * (Cin / fin_G) : 0.0;
+    fin.eps = fin_eps;
+    fin.gamma = fin_gamma;
+    fin.beta = fin_beta;
+  }
+  View vx{const_cast<float*>(x), B, H, W, Cin, pitch};
+  // the launcher's own checks before the packing (nothing is launched, the scratch stays as it is, where it refuses)
+  if (const char* why = small_out_refusal(vx, Cout, pro_scale, fin)) DM_REQUIRE(false, why);
+  int rc = small_out_pack(w_torch, Cout, Cin, wp_scratch, st);
+  if (rc == DM_OK) rc = conv3x3_small_out(vx, wp_scratch, bias, Cout, y, st, pro_scale, pro_shift, fin);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+extern "C" int dm_debug_resample2x(const float* x, int x_pitch, float* y, int y_pitch, int B, int C, int Hin, int Win,
+                                   int down, const float* pro_scale, const float* pro_shift, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !y || B <= 0 || C <= 0 || Hin <= 0 || Win <= 0 || x_pitch < C || y_pitch < C ||
+      (pro_scale != nullptr) != (pro_shift != nullptr)) {
+    set_error("bad resample2x arguments");
+    return DM_ERR_ARG;
+  }
+  View vx{const_cast<float*>(x), B, Hin, Win, C, x_pitch};
+  View vy{y, B, down ? Hin / 2 : 2 * Hin, down ? Win / 2 : 2 * Win, C, y_pitch};
+  const int rc = resample2x(vx, vy, down, pro_scale, pro_shift, st);
   if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
   return rc;
 }

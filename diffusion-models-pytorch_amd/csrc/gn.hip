@@ -344,3 +344,38 @@ int gn_apply(const View& x, int G, const double2* part, int nchunk, float eps, c
 }
 
 }  // namespace dm
+
+/* Test hooks (tests/test_gpu_norm_ops.py): one launch on the caller's device buffers; synchronous, allocate nothing.
+ * dm_debug_gn_finalize: gn_finalize on caller-provided partials [B][gn_num_chunks(HW)][G] (more than 64 chunks: the
+ * wide kernel, as in production) -> scale / shift [B][C]. dm_debug_gn_concat_stats: gn_concat_stats; an error and
+ * nothing launched where gn_concat_ok refuses. */
+extern "C" int dm_debug_gn_finalize(const void* part, int B, int HW, int C, int G, float eps, const float* gamma,
+                                    const float* beta, const float* mod_scale, const float* mod_shift, int mod_pitch,
+                                    float* scale, float* shift, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!part || !scale || !shift || B <= 0 || HW <= 0 || C <= 0 || G <= 0) {
+    set_error("bad gn_finalize arguments");
+    return DM_ERR_ARG;
+  }
+  View vx{nullptr, B, HW, 1, C, C};
+  const int rc = gn_finalize(vx, G, (const double2*)part, eps, gamma, beta, scale, shift, st, mod_scale, mod_shift,
+                             mod_pitch);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+extern "C" int dm_debug_gn_concat_stats(const void* ph, int Ch, int Gh, const void* ps, int Cs, int Gs, int B, int HW,
+                                        int G, void* out, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (!ph || !ps || !out || B <= 0 || HW <= 0 || Ch <= 0 || Cs <= 0) {
+    set_error("bad gn_concat_stats arguments");
+    return DM_ERR_ARG;
+  }
+  const int rc = gn_concat_stats((const double2*)ph, Ch, Gh, (const double2*)ps, Cs, Gs, B, HW, G, (double2*)out, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
