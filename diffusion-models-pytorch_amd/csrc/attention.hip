@@ -629,8 +629,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 // O^T rows >= Dh read clamped V rows and are not stored. Each wave owns 32 queries; NW waves per block.
 // Not bit-identical to the unfused path (exp2 and the online rescale round differently): within a few ulp of
 // the unfused softmax (tests/test_gpu_r3.py test_flash_attention_vs_unfused).
-template <int Dh, int NW>
+//  * BW > 0 (MDT's attention, models/mdt/model.py:46-52): a learned relative-position bias added to the scaled
+//    scores, softmax(q k^T d^-1/2 + bias[h]) v with bias[h][i][j] = table[h][(qy - ky + W - 1)(2W - 1) + (qx - kx +
+//    W - 1)] for tokens on a W x W grid (W <= BW). The head's (2W - 1)^2 table, pre-multiplied by log2(e), is
+//    staged in LDS once per block; the index is formed arithmetically: the query term is fixed per lane, the key
+//    term is wave-uniform per 8-key group (W % 8 == 0 as L = W^2 is a multiple of 64) and advanced incrementally.
+//    The 32 lanes of a half-wave read 32 consecutive queries against one key: W / 8 .. runs of consecutive
+//    table entries 2W - 1 apart, all within 64 dwords of each other for W <= 32, so distinct banks. The bias is
+//    added BEFORE the running maximum (s' = s sl2 + bias log2e, then the max, then exp2(s' - m)). BW = 0 is the
+//    unbiased kernel, unchanged.
+template <int Dh, int NW, int BW>
 __global__ void __launch_bounds__(NW * 64) attn_flash_kernel(AttnArgs a) {
+  constexpr bool BIAS = BW > 0;
+  constexpr int BT = BIAS ? (2 * BW - 1) * (2 * BW - 1) + 3 : 0;   // floats of the staged table
   constexpr int DHP = (Dh + 15) / 16 * 16;   // contraction depth of S (16-deep slices)
   constexpr int KB = 64;                     // keys per block
   constexpr int NS = DHP / 16;               // 16-deep slices of the S contraction
@@ -642,8 +653,9 @@ __global__ void __launch_bounds__(NW * 64) attn_flash_kernel(AttnArgs a) {
   constexpr int NDT = TAIL ? Dh / 32 : (DHP + 31) / 32;   // 32-row d tiles of O^T
   constexpr int KBUF = KB * KP, VBUF = DHP * VP, BUF = KBUF + VBUF;
   constexpr int NT = NW * 64;
-  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * BUF];
+  __shared__ __attribute__((aligned(16))) _Float16 lds[2 * BUF + 2 * BT];
   static_assert(NW * 32 * (DHP + 1) * 4 <= 2 * BUF * 2, "output staging fits the operand buffers");
+  [[maybe_unused]] const float* btab = reinterpret_cast<const float*>(lds + 2 * BUF);
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int lr = lane & 31, lh = lane >> 5;
@@ -720,6 +732,18 @@ __global__ void __launch_bounds__(NW * 64) attn_flash_kernel(AttnArgs a) {
     *reinterpret_cast<f4*>(lds + buf * BUF + row * KP + (c8 >> 1) * 32 + p * 16 + (c8 & 1) * 8) = f4{0.f, 0.f, 0.f, 0.f};
   }
 
+  // bias: the head's table into LDS (visible after the first barrier below); this lane's query term
+  [[maybe_unused]] int b_q = 0, b_k = 0, b_kx = 0, b_w2 = 0;
+  if constexpr (BIAS) {
+    const int W = a.bias_W;
+    b_w2 = 2 * W - 1;
+    const float* tb = a.bias + (size_t)(bh % a.heads) * a.bias_hs;
+    float* dstb = reinterpret_cast<float*>(lds + 2 * BUF);
+    for (int i = t; i < b_w2 * b_w2; i += NT) dstb[i] = tb[i];
+    const int q = q0 + lr, qy = q / W;
+    b_q = (qy + W - 1) * b_w2 + (q - qy * W) + W - 1 - 4 * lh;
+  }
+
   const float sl2 = ldexpf(1.f, -(a.ea + a.eb)) * 1.4426950408889634f;   // exact unscale x log2(e)
   f16v oacc[NDT];
 #pragma unroll
@@ -761,13 +785,32 @@ __global__ void __launch_bounds__(NW * 64) attn_flash_kernel(AttnArgs a) {
     // the running maximum m_run in the scaled (log2) domain, the max taken over the raw scores and scaled once
     // (sl2 > 0), each probability exp2(s sl2 - m) as one FMA and one exp2; the P scale 2^ep folded into the
     // exponent (l_run accumulates 2^ep p, undone at the end)
+    if constexpr (BIAS) {
+      // s' = s sl2 + bias log2(e) in place; accumulator rows 4 g .. + 3 of tile j are keys k8 + 4 lh + (0 .. 3) of
+      // the 8-key group k8 = 64 kb + 32 j + 8 g, one grid row (b_k = ky (2W - 1) + kx of the group's first key)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int base = b_q - b_k;
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            sacc[j][4 * g + e] = __builtin_fmaf(sacc[j][4 * g + e], sl2, btab[base - e]);
+          b_kx += 8;
+          b_k += 8;
+          if (b_kx == a.bias_W) {   // next grid row
+            b_kx = 0;
+            b_k += b_w2 - a.bias_W;
+          }
+        }
+    }
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[j][r]);
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx * sl2);
+    const float m_new = fmaxf(m_run, BIAS ? mx : mx * sl2);
     const float corr = __builtin_amdgcn_exp2f(m_run - m_new);
     m_run = m_new;
     l_run *= corr;
@@ -790,7 +833,8 @@ __global__ void __launch_bounds__(NW * 64) attn_flash_kernel(AttnArgs a) {
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float x = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[ks >> 1][8 * (ks & 1) + e], sl2, mb));
+        const float sv = sacc[ks >> 1][8 * (ks & 1) + e];
+        const float x = __builtin_amdgcn_exp2f(BIAS ? sv + mb : __builtin_fmaf(sv, sl2, mb));
         l_run += x;
         const _Float16 h0 = (_Float16)x;
         pb[ks][0][e] = h0;
@@ -907,9 +951,21 @@ bool attn_flash_ok(int L, int Dh) {
 
 template <int DH>
 static void launch_flash(const AttnArgs& a, unsigned blocks, bool nw8, hipStream_t st) {
-  if (nw8) hipLaunchKernelGGL((attn_flash_kernel<DH, 8>), dim3(blocks), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((attn_flash_kernel<DH, 2>), dim3(blocks), dim3(128), 0, st, a);
+  if (a.bias) {
+    if (a.bias_W <= 16) {
+      if (nw8) hipLaunchKernelGGL((attn_flash_kernel<DH, 8, 16>), dim3(blocks), dim3(512), 0, st, a);
+      else hipLaunchKernelGGL((attn_flash_kernel<DH, 2, 16>), dim3(blocks), dim3(128), 0, st, a);
+    } else {
+      if (nw8) hipLaunchKernelGGL((attn_flash_kernel<DH, 8, 32>), dim3(blocks), dim3(512), 0, st, a);
+      else hipLaunchKernelGGL((attn_flash_kernel<DH, 2, 32>), dim3(blocks), dim3(128), 0, st, a);
+    }
+    return;
+  }
+  if (nw8) hipLaunchKernelGGL((attn_flash_kernel<DH, 8, 0>), dim3(blocks), dim3(512), 0, st, a);
+  else hipLaunchKernelGGL((attn_flash_kernel<DH, 2, 0>), dim3(blocks), dim3(128), 0, st, a);
 }
+
+bool attn_flash_bias_ok(int L, int W) { return W >= 8 && W <= 32 && W % 8 == 0 && L == W * W; }
 
 int attn_flash(const AttnArgs& a, hipStream_t st) {
   DM_REQUIRE(attn_flash_ok(a.L, a.Dh), "flash attention: L % 64 == 0 and head dims 32, 64, 72 or 80");
@@ -920,6 +976,9 @@ int attn_flash(const AttnArgs& a, hipStream_t st) {
              "flash attention: the pre-split output image needs 32-column groups, 16-byte aligned");
   DM_REQUIRE(((reinterpret_cast<uintptr_t>(a.pq) | reinterpret_cast<uintptr_t>(a.pk) |
                reinterpret_cast<uintptr_t>(a.pv)) & 15) == 0, "flash attention: 16-byte aligned planes");
+  DM_REQUIRE(!a.bias || (attn_flash_bias_ok(a.L, a.bias_W) && a.bias_hs >= (2 * a.bias_W - 1) * (2 * a.bias_W - 1)),
+             "flash attention: the relative-position bias needs L = W^2 tokens, W a multiple of 8 up to 32, and a "
+             "per-head table of (2W - 1)^2 entries");
   const bool nw8 = a.L % 256 == 0;
   const unsigned blocks = (unsigned)((long)a.B * a.heads * (a.L / (32 * (nw8 ? 8 : 2))));
   switch (a.Dh) {
@@ -990,6 +1049,32 @@ extern "C" int dm_debug_attention(const void* pq, const void* pk, const void* pv
   a.o_split = (_Float16*)o_split; a.o_split_ea = o_split_ea; a.o_ld = o_ld;
   a.range_flag = range_flag;
   const int rc = attn_fused(a, st);
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+/* Test hook (tests/test_gpu_mdt_ops.py): one attn_flash() launch with the relative-position bias, as the MDT plan
+ * issues it. dm_debug_attention's arguments (planes only) plus the bias table [heads][bias_hs] (pre-multiplied by
+ * log2(e), (2W - 1)^2 entries used per head), the grid width W and the per-head stride. A null table runs the
+ * unbiased kernel. Synchronous; allocates nothing. */
+extern "C" int dm_debug_attention_bias(const void* pq, const void* pk, const void* pv, int B, int heads, int L, int Dh,
+                                       int ea, int eb, int ep, int ev, float* out, int ldo, void* o_split,
+                                       int o_split_ea, int o_ld, int* range_flag, const float* table, int W,
+                                       int head_stride, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  if (B <= 0 || heads <= 0 || L <= 0 || Dh <= 0) { set_error("bad attention shape"); return DM_ERR_ARG; }
+  AttnArgs a{};
+  a.pq = (const _Float16*)pq; a.pk = (const _Float16*)pk; a.pv = (const _Float16*)pv;
+  a.B = B; a.heads = heads; a.L = L; a.Dh = Dh;
+  a.ea = ea; a.eb = eb; a.ep = ep; a.ev = ev;
+  a.out = out; a.ldo = ldo;
+  a.o_split = (_Float16*)o_split; a.o_split_ea = o_split_ea; a.o_ld = o_ld;
+  a.range_flag = range_flag;
+  a.bias = table; a.bias_W = W; a.bias_hs = head_stride;
+  if (!attn_flash_ok(L, Dh)) { set_error("not a flash attention shape"); return DM_ERR_ARG; }
+  const int rc = attn_flash(a, st);
   if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
   return rc;
 }

@@ -14,6 +14,12 @@
 //   -> fc2 GEMM, x += gate_mlp * (.)
 // so norm1/norm2/modulate/gate never materialise. All GEMMs are the fp32 MFMA
 // kernel of gemm.hip.
+//
+// MDTv2 (models/mdt/model.py:246-501, inference) is the same model object and the same per-block emission
+// (build_plan's emit_block) with three additions: a learned relative-position bias inside every attention (the
+// flash kernel's BW > 0 form, or softmax_rows_bias), skip_linear(cat[x, skip]) in front of the en_outblocks and
+// de_blocks (emit_skip: one K = 2 D GEMM behind linear_presplit_cat), and the topology en_inblocks ->
+// en_outblocks (skips popped last in, first out) -> + decoder_pos_embed -> de_blocks (skip = the embedded input).
 #include <cmath>
 #include <memory>
 #include <vector>
@@ -29,9 +35,30 @@ namespace {
 
 struct BlockP {
   size_t qkv_w, qkv_b, proj_w, proj_b, fc1_w, fc1_b, fc2_w, fc2_b;
+  // MDT (models/mdt/model.py:187-220): the block's relative-position bias table, transposed to [heads][bias_hs]
+  // ((2W - 1)^2 entries used), once x log2(e) for the flash kernel and once in natural units for softmax_rows_bias;
+  // skip_linear [D][2D] + bias where the block has one
+  size_t bias_l2 = (size_t)-1, bias_nat = (size_t)-1, bias_raw = (size_t)-1;
+  size_t skip_w = (size_t)-1, skip_b = (size_t)-1;
 };
 
+constexpr size_t kNone = (size_t)-1;
+
 int dit_count(const dm_dit_arch& a) { return 8 + 10 * a.depth + 4; }
+int mdt_half_depth(const dm_mdt_arch& a) { return (a.depth - a.decode_layer) / 2; }
+// 10 leading tensors, 11 per block (2 * half_depth + decode_layer + the side block), skip_linear.{weight,bias} in
+// the en_outblocks and de_blocks, 4 of the final layer
+int mdt_count(const dm_mdt_arch& a) {
+  const int hd = mdt_half_depth(a);
+  return 10 + 11 * (2 * hd + a.decode_layer + 1) + 2 * (hd + a.decode_layer) + 4;
+}
+dm_dit_arch mdt_base(const dm_mdt_arch& a) {
+  dm_dit_arch d{};
+  d.input_size = a.input_size; d.patch_size = a.patch_size; d.in_channels = a.in_channels;
+  d.hidden_size = a.hidden_size; d.depth = a.depth; d.num_heads = a.num_heads; d.mlp_hidden = a.mlp_hidden;
+  d.num_classes = a.num_classes; d.null_class = a.null_class; d.learn_sigma = a.learn_sigma;
+  return d;
+}
 
 int dit_validate(const dm_dit_arch* a) {
   DM_REQUIRE(a != nullptr, "arch is null");
@@ -47,10 +74,26 @@ int dit_validate(const dm_dit_arch* a) {
   return DM_OK;
 }
 
+int mdt_validate(const dm_mdt_arch* a) {
+  DM_REQUIRE(a != nullptr, "arch is null");
+  const dm_dit_arch d = mdt_base(*a);
+  const int rc = dit_validate(&d);
+  if (rc) return rc;
+  DM_REQUIRE(a->decode_layer >= 0 && a->depth - a->decode_layer >= 2,
+             "decode_layer must leave at least one en_inblock / en_outblock pair");
+  return DM_OK;
+}
+
 }  // namespace
 
+// DiT and MDTv2 share this model: MDT (mdt true) adds the per-block bias tables, the skip_linear weights, the
+// decoder position table and the en_in / en_out / de topology of build_plan.
 struct DiTModel {
   dm_dit_arch arch;
+  bool mdt = false;
+  int half_depth = 0, decode_layer = 0;   // MDT: blocks = en_inblocks, en_outblocks, de_blocks (the executed ones)
+  int W = 0, bias_hs = 0;                 // MDT: token grid width, floats per head of a transposed bias table
+  size_t dpos = 0;                        // MDT: decoder_pos_embed
   float* arena = nullptr;
   size_t arena_floats = 0;
   int D = 0, T = 0, OC = 0, PP = 0, ada_total = 0;
@@ -113,13 +156,16 @@ struct DiTModel {
   }
 };
 
-static int dit_create(const dm_dit_arch* arch, const float* const* params, const int64_t* numels, int n_params,
-                      hipStream_t st, DiTModel** out) {
-  int rc = dit_validate(arch);
+// march null: DiT; else MDTv2 (arch = mdt_base(*march))
+static int dit_create(const dm_dit_arch* arch, const dm_mdt_arch* march, const float* const* params,
+                      const int64_t* numels, int n_params, hipStream_t st, DiTModel** out) {
+  int rc = march ? mdt_validate(march) : dit_validate(arch);
   if (rc) return rc;
   const dm_dit_arch a = *arch;
-  DM_REQUIRE(n_params == dit_count(a), "expected " + std::to_string(dit_count(a)) + " parameter tensors, got " +
-                                           std::to_string(n_params));
+  const bool mdt = march != nullptr;
+  const int want = mdt ? mdt_count(*march) : dit_count(a);
+  DM_REQUIRE(n_params == want, "expected " + std::to_string(want) + " parameter tensors, got " +
+                                   std::to_string(n_params));
   refresh_toggles();  // the model's arithmetic and range check (member initialisers) from this snapshot
   auto m = std::make_unique<DiTModel>();
   m->arch = a;
@@ -129,7 +175,15 @@ static int dit_create(const dm_dit_arch* arch, const float* const* params, const
   m->T = S * S;
   m->OC = a.learn_sigma ? 2 * C : C;
   m->PP = p * p;
-  m->ada_total = a.depth * 6 * D + 2 * D;
+  m->mdt = mdt;
+  if (mdt) {
+    m->half_depth = mdt_half_depth(*march);
+    m->decode_layer = march->decode_layer;
+    m->W = S;
+    m->bias_hs = ((2 * S - 1) * (2 * S - 1) + 63) / 64 * 64;
+  }
+  const int n_exec = mdt ? 2 * m->half_depth + m->decode_layer : a.depth;   // executed blocks
+  m->ada_total = n_exec * 6 * D + 2 * D;
   const int n_cls = a.num_classes + (a.null_class ? 1 : 0);
 
   // arena layout: everything 64-float aligned
@@ -155,6 +209,10 @@ static int dit_create(const dm_dit_arch* arch, const float* const* params, const
   };
 
   m->pos = take((int64_t)m->T * D, "pos_embed");
+  if (mdt) {
+    m->dpos = take((int64_t)m->T * D, "decoder_pos_embed");
+    take(D, "mask_token");   // training only
+  }
   m->xw = take((int64_t)D * C * p * p, "x_embedder.proj.weight");
   m->xb = take(D, "x_embedder.proj.bias");
   m->tw1 = take((int64_t)D * 256, "t_embedder.mlp.0.weight");
@@ -165,24 +223,39 @@ static int dit_create(const dm_dit_arch* arch, const float* const* params, const
   m->freqs = reserve(128);
   m->ada_w = reserve((int64_t)m->ada_total * D);
   m->ada_b = reserve(m->ada_total);
-  for (int b = 0; b < a.depth; ++b) {
+  const int n_rel = (2 * S - 1) * (2 * S - 1) + 3;   // BEiT table rows (the last 3, the cls entries, never indexed)
+  for (int b = 0; b < (mdt ? n_exec + 1 : a.depth); ++b) {
     BlockP bp;
     bp.qkv_w = take((int64_t)3 * D * D, "attn.qkv.weight");
     bp.qkv_b = take(3 * D, "attn.qkv.bias");
     bp.proj_w = take((int64_t)D * D, "attn.proj.weight");
     bp.proj_b = take(D, "attn.proj.bias");
+    if (mdt) {
+      bp.bias_raw = take((int64_t)n_rel * a.num_heads, "attn.rel_pos_bias.relative_position_bias_table");
+      bp.bias_l2 = reserve((int64_t)a.num_heads * m->bias_hs);
+      bp.bias_nat = reserve((int64_t)a.num_heads * m->bias_hs);
+    }
     bp.fc1_w = take((int64_t)Hm * D, "mlp.fc1.weight");
     bp.fc1_b = take(Hm, "mlp.fc1.bias");
     bp.fc2_w = take((int64_t)D * Hm, "mlp.fc2.weight");
     bp.fc2_b = take(D, "mlp.fc2.bias");
-    take_at((int64_t)6 * D * D, m->ada_w + (size_t)b * 6 * D * D, "adaLN_modulation.1.weight");
-    take_at(6 * D, m->ada_b + (size_t)b * 6 * D, "adaLN_modulation.1.bias");
-    m->blocks.push_back(bp);
+    if (b < n_exec) {
+      take_at((int64_t)6 * D * D, m->ada_w + (size_t)b * 6 * D * D, "adaLN_modulation.1.weight");
+      take_at(6 * D, m->ada_b + (size_t)b * 6 * D, "adaLN_modulation.1.bias");
+    } else {   // MDT's side block: loaded, never executed at inference, its modulation never computed
+      take((int64_t)6 * D * D, "sideblocks.adaLN_modulation.1.weight");
+      take(6 * D, "sideblocks.adaLN_modulation.1.bias");
+    }
+    if (mdt && b >= m->half_depth && b < n_exec) {
+      bp.skip_w = take((int64_t)D * 2 * D, "skip_linear.weight");
+      bp.skip_b = take(D, "skip_linear.bias");
+    }
+    if (b < n_exec) m->blocks.push_back(bp);
   }
   m->fin_w = take((int64_t)m->PP * m->OC * D, "final_layer.linear.weight");
   m->fin_b = take(m->PP * m->OC, "final_layer.linear.bias");
-  take_at((int64_t)2 * D * D, m->ada_w + (size_t)a.depth * 6 * D * D, "final_layer.adaLN_modulation.1.weight");
-  take_at(2 * D, m->ada_b + (size_t)a.depth * 6 * D, "final_layer.adaLN_modulation.1.bias");
+  take_at((int64_t)2 * D * D, m->ada_w + (size_t)n_exec * 6 * D * D, "final_layer.adaLN_modulation.1.weight");
+  take_at(2 * D, m->ada_b + (size_t)n_exec * 6 * D, "final_layer.adaLN_modulation.1.bias");
   if (!err.empty()) {
     set_error(err);
     return DM_ERR_ARG;
@@ -194,6 +267,25 @@ static int dit_create(const dm_dit_arch* arch, const float* const* params, const
   for (auto& c : copies) {
     DM_REQUIRE(params[c.idx] != nullptr, "null parameter pointer");
     DM_CHECK_HIP(hipMemcpyAsync(m->arena + c.dst, params[c.idx], c.n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  if (mdt) {
+    // bias tables [n_rel][heads] -> [heads][bias_hs], x log2(e) in float64 rounded once (flash) and as they are
+    DM_CHECK_HIP(hipStreamSynchronize(st));
+    const int heads = a.num_heads, used = n_rel - 3, hs = m->bias_hs;
+    std::vector<float> raw((size_t)n_rel * heads), tl2((size_t)heads * hs), tnat((size_t)heads * hs);
+    for (const BlockP& bp : m->blocks) {
+      DM_CHECK_HIP(hipMemcpy(raw.data(), m->P(bp.bias_raw), raw.size() * sizeof(float), hipMemcpyDeviceToHost));
+      std::fill(tl2.begin(), tl2.end(), 0.f);
+      std::fill(tnat.begin(), tnat.end(), 0.f);
+      for (int h = 0; h < heads; ++h)
+        for (int i = 0; i < used; ++i) {
+          const float v = raw[(size_t)i * heads + h];
+          tnat[(size_t)h * hs + i] = v;
+          tl2[(size_t)h * hs + i] = (float)((double)v * 1.4426950408889634074);
+        }
+      DM_CHECK_HIP(hipMemcpy(m->P(bp.bias_l2), tl2.data(), tl2.size() * sizeof(float), hipMemcpyHostToDevice));
+      DM_CHECK_HIP(hipMemcpy(m->P(bp.bias_nat), tnat.data(), tnat.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
   }
   *out = m.release();
   return DM_OK;
@@ -236,6 +328,16 @@ int DiTModel::build_plan(Plan& pl, int B) {
   float* mods = pl.alloc((size_t)B * ada_total * 4);
   float* a0 = pl.alloc((size_t)M * C * p * p * 4);
   float* x = pl.alloc((size_t)M * D * 4);
+  // MDT: the en_inblocks' outputs stay live as the en_outblocks' skips and the embedded input as the de_blocks'
+  // (xs[0] = x, xs[i + 1] = en_inblock i's output: each block writes a fresh matrix, so no copies), plus one
+  // working matrix for everything after them
+  std::vector<float*> xs;
+  float* xw_ = nullptr;
+  if (mdt) {
+    xs.push_back(x);
+    for (int i = 0; i < half_depth; ++i) xs.push_back(pl.alloc((size_t)M * D * 4));
+    xw_ = pl.alloc((size_t)M * D * 4);
+  }
   float2* stats = (float2*)pl.alloc((size_t)M * sizeof(float2));
   float* qkv = pl.alloc((size_t)M * 3 * D * 4);
   float* Sb = nullptr;  // score matrix of the unfused attention path (allocated on first use)
@@ -262,11 +364,13 @@ int DiTModel::build_plan(Plan& pl, int B) {
   // LayerNorm statistics for the next GEMM with the LN + modulate prologue: computed by that GEMM's
   // row_stats_split pass (statistics + prologue + split in one read of the tokens) or by row_stats
   bool stats_pending = false;
+  const float* stats_src = x;   // the token matrix the pending statistics are of
   const float ln_eps = 1e-6f;
   auto flush_stats = [&]() {
     if (!stats_pending) return;
     stats_pending = false;
-    pl.add("row_stats", 0, 4.0 * M * D, [=](hipStream_t st) { return row_stats(x, M, D, ln_eps, stats, st); });
+    const float* sx = stats_src;
+    pl.add("row_stats", 0, 4.0 * M * D, [=](hipStream_t st) { return row_stats(sx, M, D, ln_eps, stats, st); });
   };
   auto add_token_gemm = [&](GemmArgs g) {
     // nominal-batch decision (pick_M = T * kPickBatch): the same kernels at every B, so results are
@@ -283,7 +387,7 @@ int DiTModel::build_plan(Plan& pl, int B) {
       g2.ln_stats = nullptr;
       if (as_buf && linear_k32_ok(g2)) {
         _Float16* buf = as_buf;
-        if (g.ln_stats && stats_pending && g.A == x && g.lda == D && g.K == D && g.alpha == 1.0f) {
+        if (g.ln_stats && stats_pending && g.A == stats_src && g.lda == D && g.K == D && g.alpha == 1.0f) {
           stats_pending = false;
           float2* sp = stats;
           pl.add("row_stats_split", 0, 8.0 * g.M * g.K, [=](hipStream_t st) {
@@ -390,18 +494,22 @@ int DiTModel::build_plan(Plan& pl, int B) {
     add_gemm(g);
   }
 
-  auto stats_op = [&]() { stats_pending = true; };
-  for (int b = 0; b < a.depth; ++b) {
-    const BlockP bp = blocks[b];
+  auto stats_op = [&](const float* src) { stats_pending = true; stats_src = src; };
+  // One transformer block (DiT's and MDT's alike): reads xin, writes x + gate_msa * attn(..) to xmid and
+  // xmid + gate_mlp * mlp(..) to xout. DiT runs it in place (xin = xmid = xout = x); MDT's en_inblocks keep xin.
+  // bp.bias_l2 set: the attention adds the block's relative-position bias.
+  auto emit_block = [&](const BlockP& bp, int b, const float* xin, float* xmid, float* xout) {
     const float* mb = mods + (size_t)b * 6 * D;  // shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
+    const bool biased = bp.bias_l2 != kNone;
     // attention branch
-    stats_op();
-    GemmArgs gq = linear(x, D, M, bp.qkv_w, bp.qkv_b, 3 * D, D, qkv, 3 * D);
+    stats_op(xin);
+    GemmArgs gq = linear(xin, D, M, bp.qkv_w, bp.qkv_b, 3 * D, D, qkv, 3 * D);
     gq.ln_stats = stats; gq.ln_shift = mb; gq.ln_scale = mb + D; gq.ln_pitch = ada_total; gq.ln_rows = T;
     split(gq, 6, bp.qkv_w, (size_t)3 * D * D, 0);
     // flash attention (attention.hip attn_flash_kernel): the qkv GEMM's epilogue writes q * d^-1/2, k, v as
     // the fp16x2 operand planes (over the qkv buffer: same bytes), S never leaves the CU
-    const bool flash = math == 2 && gq.ws && attn_flash_ok(T, Dh) && toggles().attn != kAttnUnfused;
+    const bool flash = math == 2 && gq.ws && attn_flash_ok(T, Dh) && toggles().attn != kAttnUnfused &&
+                       (!biased || attn_flash_bias_ok(T, W));
     _Float16* planes = reinterpret_cast<_Float16*>(qkv);
     const size_t plane_n = (size_t)M * D * 2;   // fp16 elements of one operand's two planes
     if (flash) {
@@ -413,8 +521,8 @@ int DiTModel::build_plan(Plan& pl, int B) {
     add_token_gemm(gq);
     // the proj GEMM, built before the attention op: the flash kernel writes O as the proj's pre-split A image
     // only when this GEMM is the one that will read it (same predicate), else O as fp32 rows
-    GemmArgs gpj = linear(Ob, D, M, bp.proj_w, bp.proj_b, D, D, x, D);
-    gpj.res = x; gpj.ld_res = D; gpj.gate = mb + 2 * D; gpj.gate_pitch = ada_total; gpj.gate_rows = T;
+    GemmArgs gpj = linear(Ob, D, M, bp.proj_w, bp.proj_b, D, D, xmid, D);
+    gpj.res = xin; gpj.ld_res = D; gpj.gate = mb + 2 * D; gpj.gate_pitch = ada_total; gpj.gate_rows = T;
     split(gpj, 6, bp.proj_w, (size_t)D * D, 0);
     GemmArgs gpj_as = gpj;
     gpj_as.as = reinterpret_cast<const _Float16*>(Ob);
@@ -431,8 +539,14 @@ int DiTModel::build_plan(Plan& pl, int B) {
         at.o_split_ea = 6;
         at.o_ld = D;
       }
-      pl.add("attn_flash_kernel<" + std::to_string(Dh) + ">", 4.0 * B * heads * (double)T * T * Dh,
-             4.0 * M * (3.0 * D + D), [=](hipStream_t st) { return attn_flash(at, st); });
+      if (biased) {
+        at.bias = P(bp.bias_l2);
+        at.bias_W = W;
+        at.bias_hs = bias_hs;
+      }
+      pl.add(std::string(biased ? "attn_flash_bias_kernel<" : "attn_flash_kernel<") + std::to_string(Dh) + ">",
+             4.0 * B * heads * (double)T * T * Dh, 4.0 * M * (3.0 * D + D),
+             [=](hipStream_t st) { return attn_flash(at, st); });
     } else {
       if (!Sb) Sb = pl.alloc((size_t)B * heads * T * T * 4);
       // timm Attention: qkv.reshape(B, N, 3, heads, d): q / k / v of head h at columns h*d, D + h*d, 2D + h*d
@@ -446,7 +560,16 @@ int DiTModel::build_plan(Plan& pl, int B) {
       add_gemm(gs);
       const long rows = (long)B * heads * T;
       const int L = T;
-      pl.add("softmax_rows", 0, 8.0 * rows * L, [=](hipStream_t st) { return softmax_rows(Sb, rows, L, L, st); });
+      float* Sb_ = Sb;
+      if (biased) {
+        const float* tab = P(bp.bias_nat);
+        const int W_ = W, hs_ = bias_hs;
+        pl.add("softmax_rows_bias", 0, 8.0 * rows * L, [=](hipStream_t st) {
+          return softmax_rows_bias(Sb_, rows, L, L, tab, W_, hs_, heads, st);
+        });
+      } else {
+        pl.add("softmax_rows", 0, 8.0 * rows * L, [=](hipStream_t st) { return softmax_rows(Sb_, rows, L, L, st); });
+      }
       GemmArgs go{};
       go.M = T; go.N = Dh; go.K = T; go.Z1 = B; go.Z2 = heads; go.pick_Z = (long)kPickBatch * heads;
       go.A = Sb; go.a_s1 = (long)heads * T * T; go.a_s2 = (long)T * T; go.lda = T;
@@ -461,14 +584,14 @@ int DiTModel::build_plan(Plan& pl, int B) {
     else
       add_token_gemm(gpj);
     // MLP branch
-    stats_op();
+    stats_op(xmid);
     {
-      GemmArgs g = linear(x, D, M, bp.fc1_w, bp.fc1_b, Hm, D, hb, Hm);
+      GemmArgs g = linear(xmid, D, M, bp.fc1_w, bp.fc1_b, Hm, D, hb, Hm);
       g.ln_stats = stats; g.ln_shift = mb + 3 * D; g.ln_scale = mb + 4 * D; g.ln_pitch = ada_total; g.ln_rows = T;
       g.act = 2;
       split(g, 6, bp.fc1_w, (size_t)Hm * D, 0);
-      GemmArgs g2 = linear(hb, Hm, M, bp.fc2_w, bp.fc2_b, D, Hm, x, D);
-      g2.res = x; g2.ld_res = D; g2.gate = mb + 5 * D; g2.gate_pitch = ada_total; g2.gate_rows = T;
+      GemmArgs g2 = linear(hb, Hm, M, bp.fc2_w, bp.fc2_b, D, Hm, xout, D);
+      g2.res = xmid; g2.ld_res = D; g2.gate = mb + 5 * D; g2.gate_pitch = ada_total; g2.gate_rows = T;
       split(g2, 6, bp.fc2_w, (size_t)D * Hm, 0);
       // fc1's epilogue writes GELU(h) as fc2's pre-split A image (over hb: same bytes), no split pass for fc2
       GemmArgs g1s = g, g2s = g2;
@@ -483,12 +606,80 @@ int DiTModel::build_plan(Plan& pl, int B) {
         add_token_gemm(g2);
       }
     }
+  };
+  // MDT: out = skip_linear(cat[cur, skip]) (mdt/model.py:211-212), no residual; out may be cur. On linear_k32 the A
+  // pre-split pass does the concat (linear_presplit_cat) and one K = 2 D GEMM runs against the weight pre-split
+  // as [D][2D]; otherwise two chained GEMMs over the weight's column halves, through Ob (free between blocks).
+  auto emit_skip = [&](const BlockP& bp, const float* cur, const float* skip, float* out) {
+    flush_stats();
+    {
+      GemmArgs g = linear(cur, 2 * D, M, bp.skip_w, bp.skip_b, D, 2 * D, out, D);
+      split(g, 6, bp.skip_w, (size_t)D * 2 * D, 0);
+      if (g.ws && presplit_on && g.pick_M >= 4096 && D % 32 == 0) {
+        const size_t need = (size_t)M * 2 * D * 4;
+        if (need > as_bytes) {
+          as_buf = reinterpret_cast<_Float16*>(pl.alloc(need));
+          as_bytes = need;
+        }
+        g.as = as_buf;
+        if (as_buf && linear_k32_ok(g)) {
+          _Float16* buf = as_buf;
+          int* rf = g.range_flag;
+          const int D_ = D;
+          pl.add("linear_presplit_cat", 0, 16.0 * M * D, [=](hipStream_t st) {
+            return linear_presplit_cat(cur, skip, M, D_, 6, buf, rf, st);
+          });
+          add_gemm(g);
+          return;
+        }
+      }
+    }
+    auto half = [&](const float* A, size_t woff, bool bias, float* res, float* C) {
+      GemmArgs g = linear(A, D, M, bp.skip_w + woff, bias ? bp.skip_b : kNone, D, D, C, D);
+      g.ldb = 2 * D;
+      g.res = res; g.ld_res = D;
+      if (math == 2) {   // one exponent for both halves: that of the whole [D][2D] matrix
+        auto it = w_exp.find(P(bp.skip_w));
+        if (it == w_exp.end())
+          it = w_exp.emplace(P(bp.skip_w), split_weight_exponent(P(bp.skip_w), (size_t)D * 2 * D)).first;
+        g.split = 2; g.split_ea = 6; g.split_eb = it->second; g.range_flag = range_flag;
+      }
+      add_gemm(g);
+    };
+    half(cur, 0, true, nullptr, Ob);
+    half(skip, D, false, Ob, out);
+  };
+  float* xf = x;   // the final layer's input
+  if (!mdt) {
+    for (int b = 0; b < a.depth; ++b) emit_block(blocks[b], b, x, x, x);
+  } else {
+    // mdt/model.py:473-497: en_inblocks (outputs kept as skips), en_outblocks (skips popped last in, first out),
+    // + decoder_pos_embed, de_blocks (each with the embedded input as its skip)
+    const int hd = half_depth;
+    for (int i = 0; i < hd; ++i) emit_block(blocks[i], i, xs[i], xw_, xs[i + 1]);
+    const float* cur = xs[hd];
+    for (int j = 0; j < hd; ++j) {
+      emit_skip(blocks[hd + j], cur, xs[hd - j], xw_);
+      emit_block(blocks[hd + j], hd + j, xw_, xw_, xw_);
+      cur = xw_;
+    }
+    {
+      const float* tab = P(dpos);
+      float* xd = xw_;
+      const int D_ = D, T_ = T;
+      pl.add("add_rows_mod", 0, 8.0 * M * D, [=](hipStream_t st) { return add_rows_mod(xd, tab, M, D_, T_, st); });
+    }
+    for (int d = 0; d < decode_layer; ++d) {
+      emit_skip(blocks[2 * hd + d], xw_, xs[0], xw_);
+      emit_block(blocks[2 * hd + d], 2 * hd + d, xw_, xw_, xw_);
+    }
+    xf = xw_;
   }
   // --- final layer (dit/model.py:138-142) + unpatchify
-  stats_op();
+  stats_op(xf);
   {
-    const float* mf = mods + (size_t)a.depth * 6 * D;  // shift, scale
-    GemmArgs g = linear(x, D, M, fin_w, fin_b, PP * OC, D, lin, PP * OC);
+    const float* mf = mods + (size_t)blocks.size() * 6 * D;  // shift, scale
+    GemmArgs g = linear(xf, D, M, fin_w, fin_b, PP * OC, D, lin, PP * OC);
     g.ln_stats = stats; g.ln_shift = mf; g.ln_scale = mf + D; g.ln_pitch = ada_total; g.ln_rows = T;
     split(g, 6, fin_w, (size_t)PP * OC * D, 0);
     add_token_gemm(g);
@@ -521,7 +712,7 @@ extern "C" int dm_dit_create(const dm_dit_arch* arch, const float* const* params
                              int n_params, void* stream, dm_dit** out) {
   if (!out || !params || !numels) { dm::set_error("null argument"); return DM_ERR_ARG; }
   dm::DiTModel* m = nullptr;
-  int rc = dm::dit_create(arch, params, numels, n_params, (hipStream_t)stream, &m);
+  int rc = dm::dit_create(arch, nullptr, params, numels, n_params, (hipStream_t)stream, &m);
   if (rc) return rc;
   *out = new dm_dit{m};
   return DM_OK;
@@ -678,6 +869,63 @@ extern "C" int dm_dit_plan_stats(const dm_dit* h, int64_t* builds, int* cached) 
 }
 
 extern "C" void dm_dit_destroy(dm_dit* h) {
+  if (!h) return;
+  (void)hipDeviceSynchronize();
+  delete h->m;
+  delete h;
+}
+
+// ===========================================================================
+// C ABI: MDTv2 (the same model object and the same calls as dm_dit_*)
+// ===========================================================================
+struct dm_mdt {
+  dm::DiTModel* m;
+};
+
+extern "C" int dm_mdt_param_count(const dm_mdt_arch* arch, int* n_params) {
+  int rc = dm::mdt_validate(arch);
+  if (rc) return rc;
+  if (!n_params) { dm::set_error("n_params is null"); return DM_ERR_ARG; }
+  *n_params = dm::mdt_count(*arch);
+  return DM_OK;
+}
+
+extern "C" int dm_mdt_create(const dm_mdt_arch* arch, const float* const* params, const int64_t* numels,
+                             int n_params, void* stream, dm_mdt** out) {
+  if (!out || !params || !numels || !arch) { dm::set_error("null argument"); return DM_ERR_ARG; }
+  const dm_dit_arch base = dm::mdt_base(*arch);
+  dm::DiTModel* m = nullptr;
+  int rc = dm::dit_create(&base, arch, params, numels, n_params, (hipStream_t)stream, &m);
+  if (rc) return rc;
+  *out = new dm_mdt{m};
+  return DM_OK;
+}
+
+#define DM_MDT_FWD(h) dm_dit d_{(h) ? (h)->m : nullptr}
+
+extern "C" int dm_mdt_forward(dm_mdt* h, const float* x, const int64_t* t, const int64_t* y, int B, float* out,
+                              void* stream) {
+  DM_MDT_FWD(h);
+  return dm_dit_forward(&d_, x, t, y, B, out, stream);
+}
+extern "C" int dm_mdt_set_range_deferred(dm_mdt* h, int deferred) { DM_MDT_FWD(h); return dm_dit_set_range_deferred(&d_, deferred); }
+extern "C" int dm_mdt_range_poll(dm_mdt* h, void* stream, int* flagged) { DM_MDT_FWD(h); return dm_dit_range_poll(&d_, stream, flagged); }
+extern "C" int dm_mdt_range_fallback(dm_mdt* h, int on) { DM_MDT_FWD(h); return dm_dit_range_fallback(&d_, on); }
+extern "C" int dm_mdt_range_stats(const dm_mdt* h, int64_t* fallbacks, int* active) { DM_MDT_FWD(h); return dm_dit_range_stats(&d_, fallbacks, active); }
+extern "C" int dm_mdt_set_math(dm_mdt* h, int kind) { DM_MDT_FWD(h); return dm_dit_set_math(&d_, kind); }
+extern "C" int dm_mdt_get_math(const dm_mdt* h, int* kind) { DM_MDT_FWD(h); return dm_dit_get_math(&d_, kind); }
+extern "C" int dm_mdt_set_time_freqs(dm_mdt* h, const float* freqs, int n, void* stream) { DM_MDT_FWD(h); return dm_dit_set_time_freqs(&d_, freqs, n, stream); }
+extern "C" int dm_mdt_profile(dm_mdt* h, int enable) { DM_MDT_FWD(h); return dm_dit_profile(&d_, enable); }
+extern "C" int dm_mdt_profile_count(dm_mdt* h, int* n_ops) { DM_MDT_FWD(h); return dm_dit_profile_count(&d_, n_ops); }
+extern "C" int dm_mdt_profile_get(dm_mdt* h, int i, char* label, int label_len, double* flops, double* bytes,
+                                  double* ms_total, int64_t* launches) {
+  DM_MDT_FWD(h);
+  return dm_dit_profile_get(&d_, i, label, label_len, flops, bytes, ms_total, launches);
+}
+extern "C" int dm_mdt_memory(const dm_mdt* h, int64_t* weight_bytes, int64_t* workspace_bytes) { DM_MDT_FWD(h); return dm_dit_memory(&d_, weight_bytes, workspace_bytes); }
+extern "C" int dm_mdt_plan_stats(const dm_mdt* h, int64_t* builds, int* cached) { DM_MDT_FWD(h); return dm_dit_plan_stats(&d_, builds, cached); }
+
+extern "C" void dm_mdt_destroy(dm_mdt* h) {
   if (!h) return;
   (void)hipDeviceSynchronize();
   delete h->m;

@@ -373,6 +373,16 @@ int gemm_pick(const GemmArgs& g);
 std::string gemm_label(const GemmArgs& g);
 int timestep_embed(const int64_t* t, int B, int dim, int kind, const float* freqs, float* out, hipStream_t st);
 int softmax_rows(float* x, long rows, int L, int ld, hipStream_t st);
+// softmax_rows over x + bias: row r = (image, head h = (r / L) % heads, query i = r % L) of an L = W^2 token grid,
+// bias[j] = table[h * hs + (iy - jy + W - 1)(2W - 1) + (ix - jx + W - 1)] (natural units), the unfused form of
+// AttnArgs::bias
+int softmax_rows_bias(float* x, long rows, int L, int ld, const float* table, int W, int hs, int heads, hipStream_t st);
+// x[m][:] += tab[m % T][:] (MDT's decoder_pos_embed), D % 4 == 0
+int add_rows_mod(float* x, const float* tab, long rows, int D, int T, hipStream_t st);
+// the pre-split A image of [x | skip] (K = 2 D columns, 2^ea-scaled fp16x2 pieces, linear_presplit_a's layout and
+// expressions): the concat of MDT's skip_linear never materialises in fp32
+int linear_presplit_cat(const float* x, const float* skip, long M, int D, int ea, _Float16* out, int* range_flag,
+                        hipStream_t st);
 
 // Fused attention core (attention.hip): per (image, head) S = (alpha q)(b_scale k)^T, softmax rows,
 // O = P v with S kept on the CU, fp16x2 split operands (exponents ea / eb for S, ep / ev for PV, as
@@ -399,8 +409,14 @@ struct AttnArgs {
   // columns h Dh ..): the output projection reads it without a split pass
   _Float16* o_split;
   int o_split_ea, o_ld;
+  // flash kernel only: additive relative-position bias of a bias_W x bias_W token grid (L = bias_W^2), head h's
+  // table at bias + h * bias_hs: (2 bias_W - 1)^2 floats, entry (qy - ky + W - 1)(2W - 1) + (qx - kx + W - 1),
+  // pre-multiplied by log2(e). Null: no bias.
+  const float* bias;
+  int bias_W, bias_hs;
 };
 bool attn_fused_ok(int L, int Dh);
+bool attn_flash_bias_ok(int L, int W);
 int attn_fused(const AttnArgs& a, hipStream_t st);
 // Folded single-head attention block (attn_block.hip): T = xn At^T + w, S = T xn^T, P = softmax(S),
 // y = x + Wg' (P xn) + cb (Wg = Wp Wv), GroupNorm statistics of y.

@@ -608,6 +608,73 @@ int timestep_embed(const int64_t* t, int B, int dim, int kind, const float* freq
   return DM_OK;
 }
 
+// softmax_rows with MDT's relative-position bias added to the scores first (the unfused form of the flash kernel's
+// BIAS path): one wave per row, in place. Row = (image, head, query i) of a W x W token grid; key j's bias is
+// table[h][(iy - jy + W - 1)(2W - 1) + (ix - jx + W - 1)].
+__global__ void softmax_rows_bias_kernel(float* __restrict__ x, long rows, int L, int ld, const float* __restrict__ table,
+                                         int W, int hs, int heads) {
+  const long row = (long)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  float* r = x + row * ld;
+  const int i = (int)(row % L), h = (int)((row / L) % heads);
+  const int W2 = 2 * W - 1;
+  const int iy = i / W;
+  const int qterm = (iy + W - 1) * W2 + (i - iy * W) + W - 1;
+  const float* tb = table + (size_t)h * hs;
+  float mx = -INFINITY;
+  for (int j = lane; j < L; j += 64) {
+    const int jy = j / W;
+    const float v = r[j] + tb[qterm - (jy * W2 + (j - jy * W))];
+    r[j] = v;
+    mx = fmaxf(mx, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  float sum = 0.f;
+  for (int j = lane; j < L; j += 64) {
+    const float e = expf(r[j] - mx);
+    r[j] = e;
+    sum += e;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+  const float inv = 1.0f / sum;
+  for (int j = lane; j < L; j += 64) r[j] *= inv;
+}
+
+__global__ void add_rows_mod_kernel(float* __restrict__ x, const float* __restrict__ tab, long n4, int D4, int T) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const long m = i / D4;
+  const int c = (int)(i - m * D4);
+  f4* p = reinterpret_cast<f4*>(x) + i;
+  *p = *p + reinterpret_cast<const f4*>(tab)[(size_t)(m % T) * D4 + c];
+}
+
+int softmax_rows_bias(float* x, long rows, int L, int ld, const float* table, int W, int hs, int heads, hipStream_t st) {
+  DM_REQUIRE(rows > 0 && L > 0 && ld >= L && table && W > 0 && L == W * W && heads > 0 && rows % ((long)L * heads) == 0 &&
+                 hs >= (2 * W - 1) * (2 * W - 1),
+             "softmax with bias: rows of (image, head, query) over an L = W^2 grid and a (2W - 1)^2 table per head");
+  const long blocks = (rows + 3) / 4;
+  DM_REQUIRE(blocks < (1L << 31), "softmax: too many rows");
+  hipLaunchKernelGGL(softmax_rows_bias_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, rows, L, ld, table, W, hs,
+                     heads);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
+int add_rows_mod(float* x, const float* tab, long rows, int D, int T, hipStream_t st) {
+  DM_REQUIRE(rows > 0 && D > 0 && D % 4 == 0 && T > 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(tab)) & 15) == 0,
+             "add_rows_mod: D % 4 == 0 and 16-byte aligned rows");
+  const long n4 = rows * (D / 4);
+  const long blocks = (n4 + 255) / 256;
+  DM_REQUIRE(blocks < (1L << 31), "add_rows_mod: too many rows");
+  hipLaunchKernelGGL(add_rows_mod_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, tab, n4, D / 4, T);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
 int softmax_rows(float* x, long rows, int L, int ld, hipStream_t st) {
   DM_REQUIRE(rows > 0 && L > 0 && ld >= L, "softmax: bad shape");
   const long blocks = (rows + 3) / 4;

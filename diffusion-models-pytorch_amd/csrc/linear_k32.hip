@@ -270,6 +270,29 @@ __global__ void __launch_bounds__(256) presplit_a_kernel(GemmArgs g, void* out_)
   if (bad && g.range_flag) *g.range_flag = 1;
 }
 
+// linear_presplit_cat: presplit_a_kernel (no prologue, alpha 1) over the concatenation [x | skip] of two [M][D]
+// matrices: channel c of the K = 2 D wide row comes from x for c < D, from skip beyond (D % 8 == 0: a k-group never
+// straddles the two), so MDT's skip_linear(cat[x, skip]) is one K = 2 D GEMM with no concat in memory.
+__global__ void __launch_bounds__(256) presplit_cat_kernel(const float* __restrict__ x, const float* __restrict__ skip,
+                                                           long M, int D, int ea, void* out_, int* range_flag) {
+  _Float16* out = reinterpret_cast<_Float16*>(out_);
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const int K = 2 * D, per_row = K / 8;
+  if (i >= M * per_row) return;
+  const long m = i / per_row;
+  const int c = (int)(i - m * per_row) * 8;
+  const float* a = c < D ? x + (size_t)m * D + c : skip + (size_t)m * D + (c - D);
+  const f4 v0 = *reinterpret_cast<const f4*>(a), v1 = *reinterpret_cast<const f4*>(a + 4);
+  const float apow = ldexpf(1.f, ea);
+  bool bad = false;
+  f16x8 pc[2];
+  Split<2>::split(v0 * apow, v1 * apow, pc, bad);
+  _Float16* dst = out + (size_t)m * 2 * K + (c / 32) * 64 + ((c % 32) / 8) * 8;
+  *reinterpret_cast<f16x8*>(dst) = pc[0];
+  *reinterpret_cast<f16x8*>(dst + 32) = pc[1];
+  if (bad && range_flag) *range_flag = 1;
+}
+
 // 128 x 128 blocks of four 128 x 32 wave tiles (the 8-wave 128 x 256 and the 128 x 64 forms measured -2 % and -7 %
 // on DiT-XL/2 and were removed in round 5)
 template <int PRO>
@@ -691,6 +714,20 @@ int linear_presplit_a(const GemmArgs& g, _Float16* out, hipStream_t st) {
     hipLaunchKernelGGL(presplit_a_kernel<2>, dim3(blocks), dim3(256), 0, st, g, (void*)out);
   else
     hipLaunchKernelGGL(presplit_a_kernel<0>, dim3(blocks), dim3(256), 0, st, g, (void*)out);
+  DM_LAUNCH_CHECK();
+  return DM_OK;
+}
+
+int linear_presplit_cat(const float* x, const float* skip, long M, int D, int ea, _Float16* out, int* range_flag,
+                        hipStream_t st) {
+  DM_REQUIRE(M > 0 && D > 0 && D % 32 == 0 &&
+                 ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(skip) | reinterpret_cast<uintptr_t>(out)) & 15) == 0,
+             "linear_presplit_cat: D % 32 == 0 and 16-byte aligned rows");
+  const long n = M * (2 * D / 8);
+  const long blocks = (n + 255) / 256;
+  DM_REQUIRE(blocks < (1L << 31), "linear_presplit_cat: too many rows");
+  hipLaunchKernelGGL(presplit_cat_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, skip, M, D, ea, (void*)out,
+                     range_flag);
   DM_LAUNCH_CHECK();
   return DM_OK;
 }

@@ -62,6 +62,11 @@ class DiTArch(ctypes.Structure):
     ]
 
 
+class MDTArch(ctypes.Structure):
+    """dm_mdt_arch (include/dm_hip.h): dm_dit_arch's fields plus decode_layer."""
+    _fields_ = DiTArch._fields_ + [('decode_layer', ctypes.c_int)]
+
+
 class VaeArch(ctypes.Structure):
     """dm_vae_arch (include/dm_hip.h)."""
     _fields_ = [
@@ -308,6 +313,15 @@ def _declare(L: ctypes.CDLL):
     L.dm_dit_memory.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     L.dm_dit_destroy.argtypes = [vp]
     L.dm_dit_destroy.restype = None
+    L.dm_mdt_param_count.argtypes = [ctypes.POINTER(MDTArch), ctypes.POINTER(ctypes.c_int)]
+    L.dm_mdt_create.argtypes = [ctypes.POINTER(MDTArch), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
+                                ctypes.c_int, vp, ctypes.POINTER(vp)]
+    for name in ('forward', 'set_time_freqs', 'profile', 'profile_count', 'profile_get', 'memory', 'destroy',
+                 'range_fallback', 'range_stats', 'set_range_deferred', 'range_poll', 'set_math', 'get_math',
+                 ):   # as their dm_dit_* namesakes
+        getattr(L, 'dm_mdt_' + name).argtypes = getattr(L, 'dm_dit_' + name).argtypes
+    L.dm_mdt_destroy.restype = None
+    L.dm_mdt_plan_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int)]
     L.dm_vae_decoder_param_count.argtypes = [ctypes.POINTER(VaeArch), ctypes.POINTER(ctypes.c_int)]
     L.dm_vae_decoder_create.argtypes = [ctypes.POINTER(VaeArch), ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_int64),
                                         ctypes.c_int, vp, ctypes.POINTER(vp)]
@@ -551,17 +565,17 @@ def pack_conv_weight_wino(wp: torch.Tensor, Cin: int, Cin2: int = 0, fold: bool 
     return out
 
 
-def dit_math(handle, kind: Optional[str] = None) -> str:
-    """Set (kind given) and return the GEMM arithmetic of a native DiT handle: 'fp16x2' (default) or
-    'fp32' (dm_dit_set_math / dm_dit_get_math)."""
+def dit_math(handle, kind: Optional[str] = None, abi: str = 'dm_dit') -> str:
+    """Set (kind given) and return the GEMM arithmetic of a native DiT (abi 'dm_mdt': MDT) handle: 'fp16x2'
+    (default) or 'fp32' (dm_dit_set_math / dm_dit_get_math)."""
     L = load()
     kinds = {'fp32': 0, 'fp16x2': SPLIT_FP16X2}
     if kind is not None:
         if kind not in kinds:
             raise ValueError(f'DiT math must be one of {sorted(kinds)}')
-        check(L.dm_dit_set_math(handle, kinds[kind]), 'dm_dit_set_math')
+        check(getattr(L, abi + '_set_math')(handle, kinds[kind]), abi + '_set_math')
     k = ctypes.c_int()
-    check(L.dm_dit_get_math(handle, ctypes.byref(k)), 'dm_dit_get_math')
+    check(getattr(L, abi + '_get_math')(handle, ctypes.byref(k)), abi + '_get_math')
     return {v: n for n, v in kinds.items()}[k.value]
 
 

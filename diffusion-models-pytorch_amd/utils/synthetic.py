@@ -54,8 +54,13 @@ def synthetic_state_dict(state_dict_like: Dict[str, torch.Tensor], seed: int = 0
 
 
 def init_synthetic_(model: torch.nn.Module, seed: int = 0):
-    """Load the synthetic weights into `model` in place; returns their sha256."""
-    sd = synthetic_state_dict(model.state_dict(), seed)
+    """Load the synthetic weights into `model` in place; returns their sha256. An MDTv2 (a state_dict with
+    ``relative_position_index`` buffers) takes synthetic_mdt_state_dict."""
+    ref = model.state_dict()
+    if any(k.endswith('relative_position_index') for k in ref):
+        sd = synthetic_mdt_state_dict(ref, seed)
+    else:
+        sd = synthetic_state_dict(ref, seed)
     model.load_state_dict(sd)
     return state_dict_sha256(sd)
 
@@ -66,3 +71,28 @@ def state_dict_sha256(sd: Dict[str, torch.Tensor]) -> str:
         h.update(k.encode())
         h.update(v.detach().cpu().contiguous().numpy().tobytes())
     return h.hexdigest()
+
+
+def synthetic_mdt_state_dict(state_dict_like: Dict[str, torch.Tensor], seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Synthetic weights over an MDTv2 state_dict (models/mdt/model.py). The float tensors follow
+    synthetic_state_dict (the int64 ``relative_position_index`` buffers are kept as they are and consume no draws);
+    then the tensors that recipe would leave without influence are redrawn from a second PCG64 stream (seed + 1), in
+    key order: every ``relative_position_bias_table`` ~ N(0, 1) (attention logits of synthetic weights are nearly
+    flat, so a unit-scale bias decides the softmax), ``decoder_pos_embed`` ~ U(-1, 1) (the recipe's fan-in bound
+    would make it 1e-2 of the tokens it is added to) and the blocks' ``adaLN_modulation.1.bias`` ~ U(-1, 1) (gates of
+    order 1 instead of 1e-2: each block then changes the tokens enough that the long skips differ from one
+    another, so their order matters)."""
+    floats = {k: v for k, v in state_dict_like.items() if not k.endswith('relative_position_index')}
+    syn = synthetic_state_dict(floats, seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    out = {}
+    for name, ref in state_dict_like.items():
+        if name.endswith('relative_position_index'):
+            out[name] = ref.detach().clone()
+        elif name.endswith('relative_position_bias_table'):
+            out[name] = torch.from_numpy(rng.standard_normal(tuple(ref.shape), dtype=np.float32))
+        elif name == 'decoder_pos_embed' or (name.endswith('adaLN_modulation.1.bias') and 'blocks.' in name):
+            out[name] = torch.from_numpy((rng.random(tuple(ref.shape), dtype=np.float32) * 2.0 - 1.0))
+        else:
+            out[name] = syn[name]
+    return out

@@ -197,6 +197,55 @@ int dm_dit_memory(const dm_dit* m, int64_t* weight_bytes, int64_t* workspace_byt
 int dm_dit_plan_stats(const dm_dit* m, int64_t* builds, int* cached);
 void dm_dit_destroy(dm_dit* m);
 
+/* Denoiser: MDTv2 ----------------------------------------------------------
+ * Replaces models/mdt/model.py:246-501 (MDTv2.__init__ / forward at inference, enable_mask off): the DiT token
+ * path with a learned relative-position bias in every attention (model.py:46-52), U-ViT long skips
+ * (skip_linear(cat[x, skip]) in the en_outblocks, skips popped last in, first out) and decode_layer de_blocks that
+ * all take the embedded input as their skip, after `+ decoder_pos_embed`. `params` are the float32 state_dict
+ * tensors in order (the int64 relative_position_index buffers are left out; the engine forms that index
+ * arithmetically: (qy - ky + W - 1)(2W - 1) + (qx - kx + W - 1)): pos_embed, decoder_pos_embed, mask_token,
+ * x_embedder.proj.{weight,bias}, t_embedder.mlp.{0,2}.{weight,bias}, y_embedder.embedding_table.weight, then per
+ * block attn.qkv, attn.proj (weight, bias each), attn.rel_pos_bias.relative_position_bias_table, mlp.fc1, mlp.fc2,
+ * adaLN_modulation.1 and, where the block has one, skip_linear -- the blocks being en_inblocks (half_depth =
+ * (depth - decode_layer) / 2), en_outblocks (half_depth), de_blocks (decode_layer), sideblocks (1: loaded, never
+ * executed at inference, as mask_token) -- then final_layer.linear and final_layer.adaLN_modulation.1.
+ * The dm_mdt_* calls below behave as their dm_dit_* namesakes. */
+typedef struct dm_mdt_arch {
+  int input_size;    /* latent H = W */
+  int patch_size;
+  int in_channels;
+  int hidden_size;
+  int depth;
+  int num_heads;
+  int mlp_hidden;    /* int(hidden_size * mlp_ratio) */
+  int num_classes;
+  int null_class;    /* 1: the embedding table has the CFG null row num_classes (class_dropout_prob > 0) */
+  int learn_sigma;   /* out_channels = 2 * in_channels */
+  int decode_layer;  /* number of de_blocks */
+} dm_mdt_arch;
+
+typedef struct dm_mdt dm_mdt;
+
+int dm_mdt_param_count(const dm_mdt_arch* arch, int* n_params);
+int dm_mdt_create(const dm_mdt_arch* arch, const float* const* params, const int64_t* numels, int n_params,
+                  void* stream, dm_mdt** out);
+int dm_mdt_forward(dm_mdt* m, const float* x, const int64_t* t, const int64_t* y, int B, float* out, void* stream);
+int dm_mdt_set_math(dm_mdt* m, int kind);
+int dm_mdt_get_math(const dm_mdt* m, int* kind);
+int dm_mdt_set_range_deferred(dm_mdt* m, int deferred);
+int dm_mdt_range_poll(dm_mdt* m, void* stream, int* flagged);
+int dm_mdt_range_fallback(dm_mdt* m, int on);
+int dm_mdt_range_stats(const dm_mdt* m, int64_t* fallbacks, int* active_math);
+int dm_mdt_set_time_freqs(dm_mdt* m, const float* freqs, int n, void* stream);
+int dm_mdt_profile(dm_mdt* m, int enable);
+int dm_mdt_profile_count(dm_mdt* m, int* n_ops);
+int dm_mdt_profile_get(dm_mdt* m, int i, char* label, int label_len, double* flops, double* bytes,
+                       double* ms_total, int64_t* launches);
+/* workspace_bytes includes the skip buffers: half_depth + 3 token matrices of B * T * hidden_size floats. */
+int dm_mdt_memory(const dm_mdt* m, int64_t* weight_bytes, int64_t* workspace_bytes);
+int dm_mdt_plan_stats(const dm_mdt* m, int64_t* builds, int* cached);
+void dm_mdt_destroy(dm_mdt* m);
+
 /* Latent decoder: KL autoencoder -------------------------------------------
  * Replaces the decode path of the VAE the reference's DiT wraps (models/dit/autoencoder.py ->
  * diffusers AutoencoderKL.decode; the same network as models/stablediffusion/autoencoder.py:376-483 Decoder and

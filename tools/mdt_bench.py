@@ -1,0 +1,111 @@
+"""MDT-XL/2 against DiT-XL/2: forward time at the CFG batch 2B = 64 (4x32x32 latents), both models in one process,
+alternating, plus the per-launch time of the biased flash attention kernel (MDT) against the unbiased one (DiT) on the
+same (64 * 16, 256, 72) operand shape, from the plans' own per-launch profiles (dm_mdt_profile / dm_dit_profile).
+
+    python tools/mdt_bench.py [--batch 64] [--iters 10] [--rounds 3] [--json out.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'diffusion-models-pytorch_amd')]
+
+import torch  # noqa: E402
+
+import dmhip  # noqa: E402
+from dmhip._lib import check, load  # noqa: E402
+from models.dit.model import DiT_XL_2  # noqa: E402
+from models.mdt.model import MDTv2_XL_2  # noqa: E402
+from utils.synthetic import init_synthetic_  # noqa: E402
+
+
+def timed(model, args, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        model(*args)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def profile(model, abi, args, iters):
+    """Per-op ms per launch of one profiled run (events around every launch: not an end-to-end figure)."""
+    h = model.native_handle(args[0].device)
+    dmhip.unet_profile_enable(h, True, abi=abi)
+    for _ in range(iters):
+        model(*args)
+    torch.cuda.synchronize()
+    ops = dmhip.unet_profile_read(h, abi=abi)
+    dmhip.unet_profile_enable(h, False, abi=abi)
+    by = {}
+    for op in ops:
+        if op['launches']:
+            e = by.setdefault(op['label'], dict(ms_total=0.0, launches=0))
+            e['ms_total'] += op['ms_total']
+            e['launches'] += op['launches']
+    return {k: dict(v, ms_per_launch=v['ms_total'] / v['launches']) for k, v in by.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=64)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--json', type=str, default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('mdt_bench: no GPU visible (a timing needs the device)')
+    dev = torch.device('cuda', 0)
+    B = a.batch
+    g = torch.Generator().manual_seed(0)
+    args = (torch.randn((B, 4, 32, 32), generator=g).to(dev), torch.randint(0, 1000, (B, ), generator=g).to(dev),
+            torch.randint(0, 1000, (B, ), generator=g).to(dev))
+    models = {}
+    for name, f in (('DiT-XL/2', DiT_XL_2), ('MDT-XL/2', MDTv2_XL_2)):
+        m = f(input_size=32, num_classes=1000, learn_sigma=True).eval()
+        init_synthetic_(m)
+        models[name] = m.to(dev)
+        for _ in range(3):   # plan build, graph capture, warm-up
+            models[name](*args)
+    torch.cuda.synchronize()
+    res = {name: [] for name in models}
+    for _ in range(a.rounds):   # alternate, so both see the same box state
+        for name, m in models.items():
+            res[name].append(timed(m, args, a.iters))
+    out = dict(batch=B, iters=a.iters, device=torch.cuda.get_device_name(0), forward_ms=res)
+    for name, v in res.items():
+        print(f'{name} B={B}: ' + ' '.join(f'{x:.2f}' for x in v) + f' ms/forward (min {min(v):.2f})', flush=True)
+    ratio = min(res['MDT-XL/2']) / min(res['DiT-XL/2'])
+    out['mdt_over_dit'] = ratio
+    print(f'MDT-XL/2 / DiT-XL/2 = {ratio:.3f} (derived from block and skip-GEMM counts: ~1.10)')
+    prof = {'DiT-XL/2': profile(models['DiT-XL/2'], 'dm_dit', args, 3),
+            'MDT-XL/2': profile(models['MDT-XL/2'], 'dm_mdt', args, 3)}
+    out['profile'] = prof
+    for name, p in prof.items():
+        tot = sum(v['ms_total'] for v in p.values()) / 3
+        print(f'{name}: profiled ops, {tot:.2f} ms per forward in kernels')
+        for label, v in sorted(p.items(), key=lambda kv: -kv[1]['ms_total'])[:12]:
+            print(f'  {label:44s} {v["launches"] // 3:4d} launches/forward {v["ms_per_launch"] * 1e3:9.1f} us each')
+    fb = prof['MDT-XL/2'].get('attn_flash_bias_kernel<72>')
+    fu = prof['DiT-XL/2'].get('attn_flash_kernel<72>')
+    if fb and fu:
+        out['flash_bias_over_unbiased'] = fb['ms_per_launch'] / fu['ms_per_launch']
+        print(f'attn_flash_bias_kernel<72> {fb["ms_per_launch"] * 1e3:.1f} us vs attn_flash_kernel<72> '
+              f'{fu["ms_per_launch"] * 1e3:.1f} us per launch: x{out["flash_bias_over_unbiased"]:.3f}')
+    h = models['MDT-XL/2'].native_handle(dev)
+    import ctypes
+    w, ws = ctypes.c_int64(), ctypes.c_int64()
+    check(load().dm_mdt_memory(h, ctypes.byref(w), ctypes.byref(ws)), 'dm_mdt_memory')
+    out['mdt_weight_bytes'], out['mdt_workspace_bytes'] = w.value, ws.value
+    print(f'MDT-XL/2 memory: weights {w.value / 2**20:.0f} MiB, workspace {ws.value / 2**20:.0f} MiB')
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, 'w') as f:
+            json.dump(out, f, indent=1, sort_keys=True)
+
+
+if __name__ == '__main__':
+    main()
