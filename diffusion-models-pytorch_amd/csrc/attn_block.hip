@@ -84,6 +84,16 @@ __device__ __forceinline__ void split4(const f4 x, f16x4& hi, f16x4& lo) {
   }
 }
 
+// x as a value the compiler cannot see through. The O finalize needs it: left to itself the compiler converts
+// acc * sc to fp16 twice -- the piece it stores from the rounded fp32 product (v_cvt_pk_f16_f32), the one it subtracts
+// for lo from the exact product (v_fma_mixlo_f16) -- and where the two fall on different sides of a tie, hi + lo is
+// off by one ulp of hi (2^-11 of that O element; tests/test_gpu_attn_block_ops.py found one such query per image).
+// The other splits multiply by a power of two, where both conversions agree.
+__device__ __forceinline__ float opaque(float x) {
+  asm("" : "+v"(x));
+  return x;
+}
+
 __device__ __forceinline__ void mma3(const f16x8 (&a)[2], const f16x8 (&b)[2], fq& acc) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[1], b[0], acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[0], b[1], acc, 0, 0, 0);
@@ -155,7 +165,7 @@ __global__ void attn_fold_kernel(const float* __restrict__ wqkv, const float* __
 namespace {
 
 // ======================================================================================================
-// Variant 3 (default): no g GEMM. The values are xn itself and the folded projection comes after:
+// Variant 3 (DM_ATTN=3; variant 4 below, the default, runs the same arithmetic on 8 waves): no g GEMM. The values are xn itself and the folded projection comes after:
 //   y_i = x_i + Wg (sum_j P_ij xn_j) + cb        (sum_j P_ij = 1)
 // so per work-group: T (At xn_q^T), then ONE pass over the keys in chunks of 32 -- S^T for the chunk, an
 // online softmax update (running maximum / sum per query, the O accumulators rescaled), O^T += xn_K^T P^T --
@@ -447,8 +457,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
       float v[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = acc[2 * ks][qt][e] * sc;
-        v[4 + e] = acc[2 * ks + 1][qt][e] * sc;
+        v[e] = opaque(acc[2 * ks][qt][e] * sc);
+        v[4 + e] = opaque(acc[2 * ks + 1][qt][e] * sc);
       }
       split8(v, op[ks][qt][0], op[ks][qt][1]);
     }
@@ -820,8 +830,8 @@ __global__ void __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(2
       float v[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        v[e] = acc[2 * ks][e] * sc;
-        v[4 + e] = acc[2 * ks + 1][e] * sc;
+        v[e] = opaque(acc[2 * ks][e] * sc);
+        v[4 + e] = opaque(acc[2 * ks + 1][e] * sc);
       }
       split8(v, op[ks][0], op[ks][1]);
     }
@@ -1144,6 +1154,39 @@ int attn_perm_cols(const float* wg, float* wgp, int C, hipStream_t st) {
   return DM_OK;
 }
 
+size_t attn_fold_bytes(int C) {
+  const size_t CC = (size_t)C * C;
+  return (5 * CC + 2 * (size_t)C) * sizeof(float) + 2 * split_conv_weights_bytes(1, C, C, 2) + 64;
+}
+
+int attn_fold_all(const float* wqkv, const float* bqkv, const float* wproj, const float* bproj, int C, double scale,
+                  void* mem, AttnFoldW* f, hipStream_t st) {
+  DM_REQUIRE(mem && f && C > 0 && (reinterpret_cast<uintptr_t>(mem) & 15) == 0, "attention fold: workspace");
+  const size_t CC = (size_t)C * C;
+  const size_t nimg = split_conv_weights_bytes(1, C, C, 2);
+  const size_t nf = (5 * CC + 2 * (size_t)C) * sizeof(float);
+  char* base = static_cast<char*>(mem);
+  f->at = reinterpret_cast<float*>(base);
+  f->wg = f->at + CC;
+  f->w = f->wg + CC;
+  f->cb = f->w + C;
+  f->wgp = f->cb + C;
+  f->at_t = f->wgp + CC;
+  f->wg_t = f->at_t + CC;
+  f->at_img = base + ((nf + 15) & ~size_t(15));
+  f->wgp_img = static_cast<char*>(f->at_img) + nimg;
+  int rc;
+  if ((rc = attn_fold(wqkv, bqkv, wproj, bproj, C, scale, f->at, f->w, f->wg, f->cb, st)) != DM_OK ||
+      (rc = split_conv_weights(f->at, 1, C, C, C, 1, 2, f->at_img, st)) != DM_OK ||
+      (rc = attn_perm_cols(f->wg, f->wgp, C, st)) != DM_OK ||
+      (rc = split_conv_weights(f->wgp, 1, C, C, C, 1, 2, f->wgp_img, st)) != DM_OK ||
+      (rc = attn_transpose(f->at, f->at_t, C, st)) != DM_OK || (rc = attn_transpose(f->wg, f->wg_t, C, st)) != DM_OK)
+    return rc;
+  f->at_rs = split_conv_rowscale(f->at_img, 1, C, C);
+  f->wgp_rs = split_conv_rowscale(f->wgp_img, 1, C, C);
+  return DM_OK;
+}
+
 bool attn_small_ok(int L, int C, int heads) { return L == kSL && C == kBC && heads == 1; }
 
 int attn_transpose(const float* src, float* dst, int C, hipStream_t st) {
@@ -1192,3 +1235,49 @@ int attn_block(const AttnBlockArgs& a, hipStream_t st) {
 }
 
 }  // namespace dm
+
+/* Test hooks (tests/test_gpu_attn_block_ops.py): synchronous, allocate nothing. dm_debug_attn_fold_bytes: the
+ * workspace of one 256-channel block. dm_debug_attn_block: the product fold (attn_fold_all) of the block's own
+ * parameters wqkv [3 C][C], bqkv, wproj, bproj into ws (the fp32 results at AttnFoldW's offsets, dm_kernels.h), then
+ * ONE launch with the arguments the UNet plan gives it: kind 3 / 4 attn_block with that variant, 16 attn_small; any
+ * other kind, and whatever the launchers refuse, returns the launcher's error and launches nothing. GroupNorm of x from
+ * the tables gsc / gsh, or finalized in the kernel from gin_* when gin_part is set. */
+extern "C" int64_t dm_debug_attn_fold_bytes(int C) { return C > 0 ? (int64_t)dm::attn_fold_bytes(C) : 0; }
+
+extern "C" int dm_debug_attn_block(const float* wqkv, const float* bqkv, const float* wproj, const float* bproj,
+                                   double scale, const float* x, int x_pitch, const float* gsc, const float* gsh,
+                                   const void* gin_part, int gin_G, int gin_nchunk, const float* gin_gamma,
+                                   const float* gin_beta, float gin_eps, int kind, int B, int ex, float* y, int y_pitch,
+                                   void* gn_part, int gn_G, int* range_flag, void* ws, void* stream) {
+  using namespace dm;
+  refresh_toggles();
+  hipStream_t st = (hipStream_t)stream;
+  AttnFoldW fw;
+  int rc = attn_fold_all(wqkv, bqkv, wproj, bproj, 256, scale, ws, &fw, st);
+  if (rc != DM_OK) return rc;
+  AttnBlockArgs ab{};
+  ab.x = x; ab.x_pitch = x_pitch; ab.y = y; ab.y_pitch = y_pitch; ab.B = B;
+  ab.gsc = gsc; ab.gsh = gsh;
+  ab.w = fw.w; ab.cb = fw.cb;
+  if (gin_part) {
+    ab.gin_part = static_cast<const double2*>(gin_part); ab.gin_G = gin_G; ab.gin_nchunk = gin_nchunk;
+    ab.gin_gamma = gin_gamma; ab.gin_beta = gin_beta; ab.gin_eps = gin_eps;
+  }
+  if (gn_part) {
+    ab.gn_part = static_cast<double2*>(gn_part);
+    ab.gn_G = gn_G;
+  }
+  if (kind == 16) {
+    ab.at_t = fw.at_t; ab.wg_t = fw.wg_t;
+    rc = attn_small(ab, st);
+  } else {
+    ab.at_img = static_cast<const _Float16*>(fw.at_img); ab.at_rowscale = fw.at_rs;
+    ab.wg_img = static_cast<const _Float16*>(fw.wgp_img); ab.wg_rowscale = fw.wgp_rs;
+    ab.ex = ex; ab.eg = ex;
+    ab.range_flag = range_flag;
+    ab.variant = kind;
+    rc = attn_block(ab, st);
+  }
+  if (hipStreamSynchronize(st) != hipSuccess && rc == DM_OK) { set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}

@@ -420,6 +420,7 @@ bool attn_flash_bias_ok(int L, int W);
 int attn_fused(const AttnArgs& a, hipStream_t st);
 // Folded single-head attention block (attn_block.hip): T = xn At^T + w, S = T xn^T, P = softmax(S),
 // y = x + Wg' (P xn) + cb (Wg = Wp Wv), GroupNorm statistics of y.
+// Operator tests: tests/test_gpu_attn_block_ops.py through dm_debug_attn_block (attn_block.hip).
 struct AttnBlockArgs {
   const float* x;               // [B][256][x_pitch] block input (NHWC rows)
   int x_pitch;
@@ -456,6 +457,20 @@ int attn_fold(const float* wqkv, const float* bqkv, const float* wproj, const fl
 int attn_block(const AttnBlockArgs& a, hipStream_t st);
 // wgp = wg with its columns permuted within 32-groups as attn_block variant 3 reads its projection operand
 int attn_perm_cols(const float* wg, float* wgp, int C, hipStream_t st);
+// Everything a block's launches read of its folded weights, in one caller-supplied allocation of attn_fold_bytes(C)
+// (16-byte aligned). fp32, in floats from its start (CC = C C): at 0, wg CC, w 2 CC, cb 2 CC + C, wgp 2 CC + 2 C,
+// at_t 3 CC + 2 C, wg_t 4 CC + 2 C; then, 16-byte aligned, the fp16x2 fragment images of at and wgp with their row scales.
+struct AttnFoldW {
+  float *at = nullptr, *w = nullptr, *wg = nullptr, *cb = nullptr, *wgp = nullptr;
+  float *at_t = nullptr, *wg_t = nullptr;  // At, Wg transposed (attn_small)
+  void *at_img = nullptr, *wgp_img = nullptr;
+  const float *at_rs = nullptr, *wgp_rs = nullptr;
+};
+size_t attn_fold_bytes(int C);
+// attn_fold, split_conv_weights of at, attn_perm_cols, split_conv_weights of wgp, the two attn_transpose, on st (not
+// synchronised); *f points into mem
+int attn_fold_all(const float* wqkv, const float* bqkv, const float* wproj, const float* bproj, int C, double scale,
+                  void* mem, AttnFoldW* f, hipStream_t st);
 // Flash attention (attention.hip attn_flash_kernel) on pre-split planes for L % 64 == 0, head dims 32, 64, 72, 80:
 // ADM's L = 1024 / 64 blocks, DiT's 72-wide heads. attn_fused dispatches there for shapes it does not take.
 bool attn_flash_ok(int L, int Dh);

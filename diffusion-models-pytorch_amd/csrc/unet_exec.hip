@@ -133,12 +133,7 @@ struct UNetModel {
   // folded single-head attention blocks (attn_block.hip): per block's qkv weights, the fp32 products At, w,
   // Wg, cb and the fp16x2 fragment images of At and Wg' (Wg with permuted columns), made at the first fp16x2
   // plan build
-  struct FoldW {
-    float *at = nullptr, *w = nullptr, *wg = nullptr, *cb = nullptr, *wgp = nullptr;
-    float *at_t = nullptr, *wg_t = nullptr;  // At, Wg transposed (attn_small)
-    void *at_img = nullptr, *wgp_img = nullptr;
-    const float *at_rs = nullptr, *wgp_rs = nullptr;
-  };
+  using FoldW = AttnFoldW;  // (attn_fold_all, attn_block.hip)
   std::map<size_t, FoldW> folds;
   std::vector<void*> fold_mem;
   const FoldW* fold_for(const AttnP& p);
@@ -243,40 +238,22 @@ const UNetModel::FoldW* UNetModel::fold_for(const AttnP& p) {
   auto it = folds.find(p.wqkv);
   if (it != folds.end()) return it->second.at ? &it->second : nullptr;  // a failed fold stays failed
   const int C = p.C;
-  const size_t CC = (size_t)C * C;
   FoldW f;
   void* mem = nullptr;
-  const size_t nimg = split_conv_weights_bytes(1, C, C, 2);
-  const size_t nf = (5 * CC + 2 * (size_t)C) * sizeof(float);
-  if (hipMalloc(&mem, nf + 2 * nimg + 64) != hipSuccess) {
+  const size_t nb = attn_fold_bytes(C);
+  if (hipMalloc(&mem, nb) != hipSuccess) {
     (void)hipGetLastError();
     folds[p.wqkv] = FoldW{};  // plan builds stay deterministic: every later build sees the same failure
     return nullptr;
   }
   fold_mem.push_back(mem);
-  char* base = static_cast<char*>(mem);
-  f.at = reinterpret_cast<float*>(base);
-  f.wg = f.at + CC;
-  f.w = f.wg + CC;
-  f.cb = f.w + C;
-  f.wgp = f.cb + C;
-  f.at_t = f.wgp + CC;
-  f.wg_t = f.at_t + CC;
-  f.at_img = base + ((nf + 15) & ~size_t(15));
-  f.wgp_img = static_cast<char*>(f.at_img) + nimg;
   const double s = (double)p.sa * (p.sb != 0.f ? (double)p.sb : 1.0);
-  if (attn_fold(P(p.wqkv), P(p.bqkv), P(p.wproj), P(p.bproj), C, s, f.at, f.w, f.wg, f.cb, nullptr) != DM_OK ||
-      split_conv_weights(f.at, 1, C, C, C, 1, 2, f.at_img, nullptr) != DM_OK ||
-      attn_perm_cols(f.wg, f.wgp, C, nullptr) != DM_OK ||
-      split_conv_weights(f.wgp, 1, C, C, C, 1, 2, f.wgp_img, nullptr) != DM_OK ||
-      attn_transpose(f.at, f.at_t, C, nullptr) != DM_OK || attn_transpose(f.wg, f.wg_t, C, nullptr) != DM_OK ||
+  if (attn_fold_all(P(p.wqkv), P(p.bqkv), P(p.wproj), P(p.bproj), C, s, mem, &f, nullptr) != DM_OK ||
       hipDeviceSynchronize() != hipSuccess) {
     folds[p.wqkv] = FoldW{};
     return nullptr;
   }
-  f.at_rs = split_conv_rowscale(f.at_img, 1, C, C);
-  f.wgp_rs = split_conv_rowscale(f.wgp_img, 1, C, C);
-  split_bytes += nf + 2 * nimg;
+  split_bytes += nb - 64;  // (the fold results and images; not the allocation's 64 bytes of alignment slack)
   return &(folds[p.wqkv] = f);
 }
 
