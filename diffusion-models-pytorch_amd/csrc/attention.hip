@@ -5,18 +5,19 @@
 // bmm(v, attn^T)), models/adm/unet.py:347-408 (QKVAttention[Legacy]: q, k each * ch^-1/4, softmax in
 // fp32). The unfused path (gemm.hip S GEMM, softmax_rows, PV GEMM) writes S (B x heads x L x L fp32)
 // to HBM, reads and rewrites it for the softmax and reads it again for PV: 4 x 67 MB per CIFAR block
-// at B = 256. Here one block owns 32 (head dim 256) or 64 (head dim 64) query rows of one (image, head):
+// at B = 256. Here one block owns 32 (head dims 256, 512) or 64 (head dim 64) query rows of one (image, head):
 //   1. S [QT x L]: q rows and k rows staged through LDS as fp16x2 pieces (the split GEMM's operand
 //      format and exponents, split16.h), 4 waves x (QT rows x L/4 keys), 3 MFMAs per 16-deep slice;
 //   2. S -> LDS (fp32 rows), softmax per row exactly as softmax_rows (elementwise.hip): the same
 //      per-lane max / expf / sum order and the same v * (1 / sum), so P is bit-identical; P is split
 //      (x 2^14) in place into the A-operand layout of step 3;
 //   3. O [QT x Dh] = P v: v rows staged transposed ([d][key], KN4 loader of gemm.hip), waves over
-//      output columns (Dh = 256: 64 columns each; Dh = 64: 2 x 2 waves of 32 x 32).
+//      output columns (Dh = 256 / 512: 64 / 128 columns each; Dh = 64: 2 x 2 waves of 32 x 32).
 // The operand tiles of both contractions are prefetched two k steps ahead into registers.
 // Every contraction runs the same MFMA sequence in the same k order as the unfused GEMMs, so the
 // output equals the unfused path bit for bit (tests/test_gpu_parity.py test_fused_attention_bit_identical).
-// LDS (head dim 256, 32 query rows per block): 41 KB staging + 37 KB S / P rows -> two blocks per CU.
+// LDS (head dim 256, 32 query rows per block): 41 KB staging + 37 KB S / P rows -> two blocks per CU
+// (head dim 512: 74 KB + 37 KB, one block per CU).
 #include "dm_common.h"
 #include "dm_kernels.h"
 #include "mfma_tile.h"
@@ -76,9 +77,14 @@ __device__ __forceinline__ void p_store4(_Float16* prow, int lane, const f4& p, 
 
 // QT query rows per block: 32 for DH = 256 (78 KB of LDS: two blocks per CU), 64 for DH = 64 (the PV
 // wave layout needs 64 rows there). Operand tiles are prefetched two k steps ahead into registers.
+// DH = 512 (one head of 512 channels: the 256^2 DDPM UNets' 16 x 16 blocks): the S pass runs 16 k tiles instead
+// of 8, and the PV pass stages a 512-row V^T tile, each wave owning 128 output columns: 74 KB of staging + 37 KB
+// of S / P rows = 111 KB, one block per CU (the kernel's registers allow no more). The other layout, the DH = 256
+// stage run twice over the column halves of V in the 78 KB footprint, measured 6 % slower per launch (DESIGN.md
+// 4.17). Every output column is the one contraction over the keys in the same order either way.
 template <int DH, int QT>
 __global__ void __launch_bounds__(256) attn_fused_kernel(AttnArgs a) {
-  static_assert((DH == 256 && QT == 32) || (DH == 64 && QT == 64), "head dims 64 / 256");
+  static_assert(((DH == 256 || DH == 512) && QT == 32) || (DH == 64 && QT == 64), "head dims 64 / 256 / 512");
   constexpr int kAQ = QT;
   constexpr int STAGE_H = (kAQ + kAL) * kAP;      // Q + K tiles (fp16 elements)
   constexpr int VSTAGE_H = DH * kAP;              // V^T tile
@@ -209,10 +215,10 @@ __global__ void __launch_bounds__(256) attn_fused_kernel(AttnArgs a) {
   __syncthreads();
 
   // ---------------------------------------------------------------- 3. O = P v
-  // waves: DH = 256: all rows x 64 columns each; DH = 64 (64 rows): 2 x 2 waves of 32 x 32
-  constexpr int TM = DH == 256 ? kAQ / 32 : 1, TN = DH == 256 ? 2 : 1;
-  const int orow0 = DH == 256 ? 0 : (wave >> 1) * 32;
-  const int ocol0 = DH == 256 ? wave * 64 : (wave & 1) * 32;
+  // waves: DH >= 256: all rows x DH / 4 columns each; DH = 64 (64 rows): 2 x 2 waves of 32 x 32
+  constexpr int TM = DH >= 256 ? kAQ / 32 : 1, TN = DH >= 256 ? DH / 128 : 1;
+  const int orow0 = DH >= 256 ? 0 : (wave >> 1) * 32;
+  const int ocol0 = DH >= 256 ? wave * (DH / 4) : (wave & 1) * 32;
   f16v oacc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -404,18 +410,106 @@ __device__ __forceinline__ void attn_proj(const ConvArgs& c, f16v (&oacc)[2][2],
   if (c.gn_part) epi.emit(m0);
 }
 
+// attn_presplit_kernel's q tile: head-dim columns D0 .. D0 + QH - 1 of the 64 q rows (both piece planes, [row][DH]
+// fp16 at Q) into LDS rows of [16-deep slice][piece][lane group][8] fp16, pitch 2 QH + 8; UB 16-B chunks per thread
+// in flight at a time (all of them before the S loop; fewer inside it, beside the k ring and the accumulators).
+template <int DH, int QH, int D0, int UB = 2 * (64 * QH / 8) / 256>
+__device__ __forceinline__ void presplit_stage_q(const _Float16* Q, size_t plane, _Float16* Qs, int t) {
+  constexpr int QP = 2 * QH + 8;
+  constexpr int QCH = 64 * QH / 8;  // 16-B chunks of one piece plane of the tile
+  static_assert((2 * QCH / 256) % UB == 0, "whole batches");
+#pragma unroll
+  for (int u0 = 0; u0 < 2 * QCH / 256; u0 += UB) {
+    f16x8 qv[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      const int c = t + 256 * (u0 + u), piece = c / QCH, rem = c - piece * QCH;
+      const int row = rem / (QH / 8), d8 = rem - row * (QH / 8);
+      qv[u] = *reinterpret_cast<const f16x8*>(Q + piece * plane + (size_t)row * DH + D0 + 8 * d8);
+    }
+#pragma unroll
+    for (int u = 0; u < UB; ++u) {
+      const int c = t + 256 * (u0 + u), piece = c / QCH, rem = c - piece * QCH;
+      const int row = rem / (QH / 8), d8 = rem - row * (QH / 8);
+      *reinterpret_cast<f16x8*>(Qs + row * QP + (d8 >> 1) * 32 + piece * 16 + (d8 & 1) * 8) = qv[u];
+    }
+  }
+}
+
+// attn_presplit_kernel<512>'s PV pass: the DH = 256 pass (64 rows x 64 output columns per wave, v^T fragments on a
+// register ring RD slices ahead) run twice, over v^T rows / output columns 0..255 and 256..511, against the same
+// P rows in LDS. Every output column is the one contraction over the 256 keys in slice order.
+template <int RD>
+__device__ __forceinline__ void presplit_pv512(const AttnArgs& a, const float* sp, const _Float16* V, size_t plane,
+                                               int bh, int qt, int wave, int lr, int lh) {
+  constexpr int DH = 512, QT = 64, NK = kAL / 16, PPITCH = 2 * kSP;
+  const _Float16* P = reinterpret_cast<const _Float16*>(sp);
+  const float ounscale = ldexpf(1.f, -(a.ep + a.ev));
+  const int h = bh % a.heads, b = bh / a.heads;
+  float* out = a.out + ((size_t)b * kAL + qt * QT) * a.ldo + h * DH;
+#pragma unroll 1
+  for (int ocol0 = wave * 64; ocol0 < DH; ocol0 += 256) {
+    f16x8 rv[RD][2][2];
+    auto load_v = [&](int s, int slot) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          rv[slot][j][q] =
+              *reinterpret_cast<const f16x8*>(V + q * plane + (size_t)(ocol0 + j * 32 + lr) * kAL + 16 * s + 8 * lh);
+    };
+    f16v oacc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) oacc[i][j][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < RD; ++s) load_v(s, s);
+#pragma unroll
+    for (int s = 0; s < NK; ++s) {
+      const int slot = s % RD;
+      f16x8 av[2][2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          av[i][q] = *reinterpret_cast<const f16x8*>(P + (i * 32 + lr) * PPITCH + (s >> 1) * kAP + (s & 1) * 32 + lh * 16 +
+                                                     q * 8);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) Split<2>::mma(av[i], rv[slot][j], oacc[i][j]);
+      load_v(min(s + RD, NK - 1), slot);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          out[(size_t)(i * 32 + acc_row(r, lh)) * a.ldo + ocol0 + j * 32 + lr] = oacc[i][j][r] * ounscale;
+  }
+}
+
 // Pre-split operands (AttnArgs::pq / pk / pv, written by the qkv projection's epilogue): no split on the
 // VALU. q is staged once in LDS; k and v^T fragments are 16-B loads per lane from L2 riding a register
 // ring RD slices ahead of their use. (k / v^T as contiguous 1-KiB fragment images cut the block from
 // 125.6 to 110.3 us but measured 1.6 % slower end to end -- every other kernel of the forward then ran at
 // a lower clock -- so the [token][d] / [d][token] planes stay.) 64 query rows per block (75 KB of LDS for
 // the S / P rows: two blocks per CU). Same MFMA sequence as the unfused GEMMs.
+// DH = 512: the q tile is staged in two halves of the head dim (QH = 256 columns at a time: the S / P rows hold no
+// more), the S accumulators running on over slices 0..15 then 16..31, and the PV pass runs twice, over v^T rows
+// 0..255 and 256..511 (presplit_pv512): the same LDS footprint, the same contraction orders.
 template <int DH>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) attn_presplit_kernel(AttnArgs a) {
-  static_assert(DH == 64 || DH == 256, "head dims 64 / 256");
+  static_assert(DH == 64 || DH == 256 || DH == 512, "head dims 64 / 256 / 512");
   constexpr int QT = 64, NS = DH / 16, RD = 6;
+  constexpr int QH = DH == 512 ? 256 : DH;   // head-dim columns of the q tile staged at a time
   __shared__ __attribute__((aligned(16))) float sp[QT * kSP];
-  static_assert(QT * (2 * DH + 8) * 2 <= QT * kSP * 4, "the staged q tile fits the S rows");
+  static_assert(QT * (2 * QH + 8) * 2 <= QT * kSP * 4, "the staged q tile fits the S rows");
   AT_RSTAMP(6);
   AT_STAMP(0);
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -433,7 +527,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   // S is written), rows of [16-deep slice][piece][lane group][8] fp16 with a 16-B pad (an odd number of
   // 16-B slots: conflict-free fragment reads). k rows (64 per wave, no reuse) ride a register ring RD
   // slices ahead. Same operands and MFMA sequence as before: S is unchanged bit for bit.
-  constexpr int QP = 2 * DH + 8;
+  constexpr int QP = 2 * QH + 8;
   _Float16* Qs = reinterpret_cast<_Float16*>(sp);
   f16x8 rb[RD][2][2];   // [slot][tile][piece]
   auto load_k = [&](int s, int slot) {
@@ -446,22 +540,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   };
 #pragma unroll
   for (int s = 0; s < RD; ++s) load_k(min(s, NS - 1), s);
-  {
-    constexpr int QCH = 64 * DH / 8;  // 16-B chunks of one piece plane of the tile
-    f16x8 qv[2 * QCH / 256];
-#pragma unroll
-    for (int u = 0; u < 2 * QCH / 256; ++u) {
-      const int c = t + 256 * u, piece = c / QCH, rem = c - piece * QCH;
-      const int row = rem / (DH / 8), d8 = rem - row * (DH / 8);
-      qv[u] = *reinterpret_cast<const f16x8*>(Q + piece * plane + (size_t)row * DH + 8 * d8);
-    }
-#pragma unroll
-    for (int u = 0; u < 2 * QCH / 256; ++u) {
-      const int c = t + 256 * u, piece = c / QCH, rem = c - piece * QCH;
-      const int row = rem / (DH / 8), d8 = rem - row * (DH / 8);
-      *reinterpret_cast<f16x8*>(Qs + row * QP + (d8 >> 1) * 32 + piece * 16 + (d8 & 1) * 8) = qv[u];
-    }
-  }
+  presplit_stage_q<DH, QH, 0>(Q, plane, Qs, t);
   f16v acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -472,12 +551,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    const int slot = s % RD;
+    if constexpr (DH == 512) {
+      if (s == QH / 16) {  // the q tile's second half, over the first one once every wave is done reading it
+        __syncthreads();
+        presplit_stage_q<DH, QH, QH, 4>(Q, plane, Qs, t);
+        __syncthreads();
+      }
+    }
+    const int slot = s % RD, sq = s % (QH / 16);
     f16x8 av[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int q = 0; q < 2; ++q) av[i][q] = *reinterpret_cast<const f16x8*>(Qs + (i * 32 + lr) * QP + s * 32 + q * 16 + lh * 8);
+      for (int q = 0; q < 2; ++q) av[i][q] = *reinterpret_cast<const f16x8*>(Qs + (i * 32 + lr) * QP + sq * 32 + q * 16 + lh * 8);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -541,6 +627,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   AT_STAMP(2);
 
   // ---------------------------------------------------------------- 3. O = P v
+  if constexpr (DH == 512) {  // two passes of 256 output columns (presplit_pv512); no fused projection at this width
+    presplit_pv512<RD>(a, sp, V, plane, bh, qt, wave, lr, lh);
+    AT_STAMP(3);
+    return;
+  }
   constexpr int TM = DH == 256 ? 2 : 1, TN = DH == 256 ? 2 : 1, NK = kAL / 16;
   const int orow0 = DH == 256 ? 0 : (wave >> 1) * 32;
   const int ocol0 = DH == 256 ? wave * 64 : (wave & 1) * 32;
@@ -998,27 +1089,31 @@ extern "C" int dm_debug_attn_stamps(void* host, int nblocks) {
 }
 #endif
 
-bool attn_fused_ok(int L, int Dh) { return L == kAL && (Dh == 64 || Dh == 256); }
+bool attn_fused_ok(int L, int Dh) { return L == kAL && (Dh == 64 || Dh == 256 || Dh == 512); }
 
 int attn_fused(const AttnArgs& args, hipStream_t st) {
   if (!attn_fused_ok(args.L, args.Dh)) return attn_flash(args, st);
   AttnArgs a = args;
   a.proj_staged = a.fuse_proj && staged_epilogue_ok(a.proj) ? 1 : 0;
-  DM_REQUIRE(attn_fused_ok(a.L, a.Dh), "fused attention: L must be 256 and the head dim 64 or 256");
+  DM_REQUIRE(attn_fused_ok(a.L, a.Dh), "fused attention: L must be 256 and the head dim 64, 256 or 512");
   DM_REQUIRE((a.qkv || a.pq) && a.out && a.B > 0 && a.heads > 0 && a.ld % 4 == 0 && a.ldo % 4 == 0 &&
              (a.q0 + 0) % 4 == 0 && a.k0 % 4 == 0 && a.v0 % 4 == 0 && a.hs % 4 == 0,
              "fused attention: operands must be float4-aligned rows");
   if (a.pq) {
     DM_REQUIRE(a.pk && a.pv, "fused attention: all three operand planes");
     const dim3 grid(a.B * a.heads * (kAL / 64));
-    if (a.Dh == 256)
+    if (a.Dh == 512)
+      hipLaunchKernelGGL((attn_presplit_kernel<512>), grid, dim3(256), 0, st, a);
+    else if (a.Dh == 256)
       hipLaunchKernelGGL((attn_presplit_kernel<256>), grid, dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL((attn_presplit_kernel<64>), grid, dim3(256), 0, st, a);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  if (a.Dh == 256)
+  if (a.Dh == 512)
+    hipLaunchKernelGGL((attn_fused_kernel<512, 32>), dim3(a.B * a.heads * (kAL / 32)), dim3(256), 0, st, a);
+  else if (a.Dh == 256)
     hipLaunchKernelGGL((attn_fused_kernel<256, 32>), dim3(a.B * a.heads * (kAL / 32)), dim3(256), 0, st, a);
   else
     hipLaunchKernelGGL((attn_fused_kernel<64, 64>), dim3(a.B * a.heads * (kAL / 64)), dim3(256), 0, st, a);

@@ -764,8 +764,10 @@ bool conv_lds_tables(const ConvArgs& a) {
   if (!a.pro_scale || a.ws_np != 2) return false;
   if (a.taps == 1) return conv_pw_ok(a);
   if (a.taps != 9 || conv_pick(a) < 3) return false;
-  PatchGeom g;
-  conv_patch_pick(a, g);
+  // a forced K32 tile (ConvArgs::tile 10 ..) gives conv_pick() >= 3 without a halo-patch geometry: not this path
+  // (g would be read unset, and the answer would be whatever the stack held)
+  PatchGeom g{};
+  if (!conv_patch_pick(a, g)) return false;
   return conv_patch3_ok(a, conv_pick(a) + 1, g);
 }
 

@@ -95,6 +95,7 @@ struct UNetModel {
   std::vector<Node> nodes;
   std::vector<int> skip_C, skip_level;  // per skip id
   int n_levels = 0;
+  float norm_eps = 1e-5f;  // every GroupNorm's eps: nn.GroupNorm's default; variant 3: 1e-6 (pesser/model.py:33)
 
   // plan cache (LRU over (B, H, W)), scratch from a pool shared with dm_unet_share_workspace peers
   struct Plan : PlanBase {
@@ -177,7 +178,18 @@ void UNetModel::split_for(ConvArgs& c) {
   c.ws_np = 0;
   c.ws_rowscale = nullptr;
   c.range_flag = nullptr;
-  if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)))) return;
+  // a bottom/right-padded stride-2 conv (variant 3's Downsample) that conv_split_eligible turns down also gets split
+  // weights when conv_k32's stride-2 tiles would run it given them (VaeNet::split_for, vae_blocks.h)
+  bool s2seg = false;
+  if (conv_math == 2 && c.s2_pad0 && c.stride == 2 && c.taps == 9) {
+    ConvArgs t = c;
+    t.ws = reinterpret_cast<const void*>(16);  // placeholders: the shape checks only
+    t.ws_np = 2;
+    t.ws_rowscale = reinterpret_cast<const float*>(16);
+    const int v = conv_k32_pick(t);
+    s2seg = v == 9 || v == 13;
+  }
+  if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)) || s2seg)) return;
   if ((c.taps == 1 || c.stride == 2) && conv_math != 2) return;  // the split 1x1 / stride-2 paths are fp16x2 only
   const int nmat = c.upsample == 2 ? 4 : 1;
   const int ntap = c.upsample == 2 ? 4 : c.taps;
@@ -268,6 +280,7 @@ static int first_channels(const dm_unet_arch& a) { return a.variant == 2 ? a.dim
 
 // Heads of an attention block with C channels; where: 0 down path, 1 bottleneck, 2 up path.
 static int attn_heads(const dm_unet_arch& a, int C, int where) {
+  if (a.variant == 3) return 1;  // AttnBlock: one head of C channels (pesser/model.py:171-176)
   if (a.variant == 2) {  // models/adm/unet.py:296-302, 470-471, 606
     if (a.attn_head_dims > 0) return C / a.attn_head_dims;
     return where == 2 ? a.n_heads_up : a.n_heads;
@@ -278,7 +291,8 @@ static int attn_heads(const dm_unet_arch& a, int C, int where) {
 
 static int count_params(const dm_unet_arch& a) {
   // mirrors the registration order of models/unet.py:47-119 (variant 1:
-  // models/unet_categorial_adagn.py:77-163; variant 2: models/adm/unet.py:489-635)
+  // models/unet_categorial_adagn.py:77-163; variant 2: models/adm/unet.py:489-635; variant 3:
+  // models/pesser/model.py:203-285, the same tensors as variant 0 in another order: walk_order below)
   int n = 4 + 2;  // time_embed (2 linears), first conv
   if (a.variant >= 1 && a.num_classes > 0) n += 1;  // class_embed.weight / label_emb.weight
   auto rb = [](int cin, int cout) { return 10 + (cin != cout ? 2 : 0); };
@@ -323,8 +337,8 @@ static int validate_arch(const dm_unet_arch* a) {
   DM_REQUIRE(a->in_channels >= 1 && a->in_channels <= 4, "in_channels out of range (1..4)");
   DM_REQUIRE(a->out_channels >= 1 && a->out_channels <= 8, "out_channels out of range (1..8)");
   DM_REQUIRE(a->num_res_blocks >= 1, "num_res_blocks must be >= 1");
-  DM_REQUIRE(a->variant >= 0 && a->variant <= 2,
-             "variant must be 0 (UNet), 1 (UNetCategorialAdaGN) or 2 (ADM UNetModel)");
+  DM_REQUIRE(a->variant >= 0 && a->variant <= 3,
+             "variant must be 0 (UNet), 1 (UNetCategorialAdaGN), 2 (ADM UNetModel) or 3 (pesser Model)");
   if (a->variant == 0) DM_REQUIRE(a->n_heads >= 1, "n_heads must be >= 1");
   if (a->variant == 1) DM_REQUIRE(a->attn_head_dims >= 1, "attn_head_dims must be >= 1");
   if (a->variant == 2 && a->attn_head_dims <= 0)
@@ -347,6 +361,84 @@ static int validate_arch(const dm_unet_arch* a) {
   return DM_OK;
 }
 
+// Variant 3 (models/pesser/model.py) registers a level's ResnetBlocks, then its AttnBlocks, then its Downsample
+// (:220-240), and stores `up` by level (self.up.insert(0, ...), :277) although the forward runs it from the deepest
+// level (:314). order[i] = the state_dict index of the i-th tensor of the executor's walk (block, its attention,
+// ..., resample; up path deepest level first), which is variant 0's registration order.
+static std::vector<int> walk_order(const dm_unet_arch& a) {
+  auto rb = [](int cin, int cout) { return 10 + (cin != cout ? 2 : 0); };
+  const int attn = 10, L = a.n_stages, R = a.num_res_blocks;
+  std::vector<int> order;
+  auto run = [&](int first, int n) {
+    for (int i = 0; i < n; ++i) order.push_back(first + i);
+  };
+  int pos = 0;
+  run(pos, 6);  // temb.dense.{0,1}, conv_in
+  pos += 6;
+  int cur = a.dim;
+  std::vector<int> dims{cur};
+  for (int i = 0; i < L; ++i) {
+    const int out = a.dim * a.dim_mults[i];
+    std::vector<int> blk;  // first index of each block
+    int p = pos;
+    for (int j = 0; j < R; ++j) {
+      blk.push_back(p);
+      p += rb(j == 0 ? cur : out, out);
+    }
+    const int attn0 = p;
+    if (a.use_attn[i]) p += attn * R;
+    for (int j = 0; j < R; ++j) {
+      run(blk[j], rb(j == 0 ? cur : out, out));
+      if (a.use_attn[i]) run(attn0 + attn * j, attn);
+      dims.push_back(out);
+    }
+    cur = out;
+    if (i < L - 1) {
+      run(p, 2);
+      p += 2;
+      dims.push_back(out);
+    }
+    pos = p;
+  }
+  const int mid = rb(cur, cur) * 2 + attn;
+  run(pos, mid);
+  pos += mid;
+  // up levels as the forward meets them (deepest first): their block input widths, then their state_dict offsets
+  std::vector<std::vector<int>> cin(L);
+  for (int i = L - 1; i >= 0; --i) {
+    const int out = a.dim * a.dim_mults[i];
+    for (int j = 0; j < R + 1; ++j) {
+      cin[i].push_back(dims.back() + cur);
+      dims.pop_back();
+      cur = out;
+    }
+  }
+  std::vector<int> first(L);
+  for (int i = 0; i < L; ++i) {
+    first[i] = pos;
+    for (int j = 0; j < R + 1; ++j) pos += rb(cin[i][j], a.dim * a.dim_mults[i]);
+    if (a.use_attn[i]) pos += attn * (R + 1);
+    if (i > 0) pos += 2;
+  }
+  for (int i = L - 1; i >= 0; --i) {
+    const int out = a.dim * a.dim_mults[i];
+    int p = first[i];
+    std::vector<int> blk;
+    for (int j = 0; j < R + 1; ++j) {
+      blk.push_back(p);
+      p += rb(cin[i][j], out);
+    }
+    for (int j = 0; j < R + 1; ++j) {
+      run(blk[j], rb(cin[i][j], out));
+      if (a.use_attn[i]) run(p + attn * j, attn);
+    }
+    if (a.use_attn[i]) p += attn * (R + 1);
+    if (i > 0) run(p, 2);
+  }
+  run(pos, 4);  // norm_out, conv_out
+  return order;
+}
+
 // ---------------------------------------------------------------------------
 // create
 // ---------------------------------------------------------------------------
@@ -361,6 +453,23 @@ static int unet_create(const dm_unet_arch* arch, const float* const* params, con
   refresh_toggles();  // the model's arithmetic and range check (member initialisers) from this snapshot
   auto m = std::make_unique<UNetModel>();
   m->arch = a;
+  if (a.variant == 3) m->norm_eps = 1e-6f;
+  // variant 3: the caller's tensors re-ordered into the walk's order
+  std::vector<const float*> wparams;
+  std::vector<int64_t> wnumels;
+  if (a.variant == 3) {
+    const std::vector<int> order = walk_order(a);
+    DM_REQUIRE((int)order.size() == n_params, "variant 3: parameter order table does not cover the state_dict");
+    std::vector<char> seen(n_params, 0);
+    for (int idx : order) {
+      DM_REQUIRE(idx >= 0 && idx < n_params && !seen[idx], "variant 3: parameter order table is not a permutation");
+      seen[idx] = 1;
+      wparams.push_back(params[idx]);
+      wnumels.push_back(numels[idx]);
+    }
+    params = wparams.data();
+    numels = wnumels.data();
+  }
   ParamReader rd{params, numels, n_params};
   Packer pk;
   const int D = a.dim, TD = 4 * a.dim, C0 = first_channels(a);
@@ -603,6 +712,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   auto Hl = [&](int lvl) { return H >> lvl; };
   auto Wl = [&](int lvl) { return W >> lvl; };
   const int D = arch.dim, TD = 4 * arch.dim, G = 32, C0 = skip_C[0];
+  const float gn_eps = norm_eps;
 
   // --- staging of x / t / y / out
   pl.x = alloc((size_t)B * arch.in_channels * H * W * 4);
@@ -876,12 +986,12 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     // (CIFAR: <= 16 chunks per image); the 256^2 maps of ADM have 1024 and take the finalize launch
     if (conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
       c.gin_part = stp; c.gin_G = G; c.gin_nchunk = gn_num_chunks(v.H * v.W);
-      c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = 1e-5f;
+      c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = gn_eps;
       c.gin_gamma = P(gamma); c.gin_beta = P(beta); c.gin_ms = ms; c.gin_mb = mb; c.gin_mp = mp;
       return;
     }
     add("gn_finalize", 0, 8.0 * B * v.C, [=](hipStream_t st) {
-      return gn_finalize(v, G, stp, 1e-5f, self->P(gamma), self->P(beta), gsc, gsh, st, ms, mb, mp);
+      return gn_finalize(v, G, stp, gn_eps, self->P(gamma), self->P(beta), gsc, gsh, st, ms, mb, mp);
     });
   };
 
@@ -968,7 +1078,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       if (r.updown && !fuse1) {
         // normalise + SiLU + resample into a1, then a plain conv at the output resolution
         add("gn_finalize", 0, 8.0 * B * r.cin, [=](hipStream_t st) {
-          return gn_finalize(xin, G, st1, 1e-5f, self->P(r.gn1.g), self->P(r.gn1.b), gsc, gsh, st);
+          return gn_finalize(xin, G, st1, gn_eps, self->P(r.gn1.g), self->P(r.gn1.b), gsc, gsh, st);
         });
         const bool down = r.updown == 2;
         add("resample2x", 0, 4.0 * B * ((double)Hi * Wi + (double)Ho * Wo) * r.cin,
@@ -981,7 +1091,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         gn_prologue(c1, xin, st1, r.gn1.g, r.gn1.b, nullptr, nullptr, 0);
       } else {
         add("gn_apply", 0, gn_bytes(xin, true), [=](hipStream_t st) {
-          return gn_apply(xin, G, st1, nchunk, 1e-5f, self->P(r.gn1.g), self->P(r.gn1.b), nullptr, nullptr, 0, 1,
+          return gn_apply(xin, G, st1, nchunk, gn_eps, self->P(r.gn1.g), self->P(r.gn1.b), nullptr, nullptr, 0, 1,
                           va1, st);
         });
         c1.x1 = a1;
@@ -994,7 +1104,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         gn_prologue(c2, vh, st2, r.gn2.g, r.gn2.b, ms, mb, mp);
       } else {
         add("gn_apply", 0, gn_bytes(vh, true), [=](hipStream_t st) {
-          return gn_apply(vh, G, st2, nchunk_o, 1e-5f, self->P(r.gn2.g), self->P(r.gn2.b), ms, mb, mp, 1, va2, st);
+          return gn_apply(vh, G, st2, nchunk_o, gn_eps, self->P(r.gn2.g), self->P(r.gn2.b), ms, mb, mp, 1, va2, st);
         });
       }
       emit_conv(c2, y);
@@ -1024,10 +1134,10 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         const bool infin = av == 4 && C % G == 0 && !toggles().attn_gn_launch;
         if (infin) {
           ab.gin_part = sta; ab.gin_G = G; ab.gin_nchunk = gn_num_chunks(hw);
-          ab.gin_gamma = P(p.gn.g); ab.gin_beta = P(p.gn.b); ab.gin_eps = 1e-5f;
+          ab.gin_gamma = P(p.gn.g); ab.gin_beta = P(p.gn.b); ab.gin_eps = gn_eps;
         } else {
           add("gn_finalize", 0, 8.0 * B * C, [=](hipStream_t st) {
-            return gn_finalize(xin, G, sta, 1e-5f, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
+            return gn_finalize(xin, G, sta, gn_eps, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
           });
         }
         gn_ready.erase(y.p);
@@ -1055,7 +1165,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
           ab.x = xin.p; ab.x_pitch = xin.pitch; ab.y = y.p; ab.y_pitch = y.pitch; ab.B = B;
           ab.at_t = fs->at_t; ab.w = fs->w; ab.wg_t = fs->wg_t; ab.cb = fs->cb;
           ab.gin_part = sta; ab.gin_G = G; ab.gin_nchunk = gn_num_chunks(hw);
-          ab.gin_gamma = P(p.gn.g); ab.gin_beta = P(p.gn.b); ab.gin_eps = 1e-5f;
+          ab.gin_gamma = P(p.gn.g); ab.gin_beta = P(p.gn.b); ab.gin_eps = gn_eps;
           ab.gn_part = gn_buf_for(y, G);
           ab.gn_G = G;
           gn_ready.erase(y.p);
@@ -1115,7 +1225,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       const bool qkv_linear = conv_math == 2 && cq.ws && cq.ws_np == 2 && linear_k32_ok(gl);
       if (qkv_linear) {
         add("gn_finalize", 0, 8.0 * B * C, [=](hipStream_t st) {
-          return gn_finalize(xin, G, sta, 1e-5f, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
+          return gn_finalize(xin, G, sta, gn_eps, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
         });
         // GroupNorm + split of the input once (linear_presplit_a) instead of once per 128-column tile inside
         // the GEMM: one buffer shared by the attention blocks (the plan's launches are stream-ordered)
@@ -1135,7 +1245,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         add_conv(cq);
       } else {
         add("gn_finalize", 0, 8.0 * B * C, [=](hipStream_t st) {
-          return gn_finalize(xin, G, sta, 1e-5f, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
+          return gn_finalize(xin, G, sta, gn_eps, self->P(p.gn.g), self->P(p.gn.b), gsc, gsh, st);
         });
         split_gemm(gq, 6, gq.Bm, (size_t)3 * C * C);
         add_gemm(gq);
@@ -1224,6 +1334,8 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       ConvArgs c{};
       c.x1 = xin.p; c.x1_pitch = xin.pitch; c.Cin1 = n.cin; c.Hin = Hi; c.Win = Wi;
       c.taps = 9; c.stride = n.kind == N_DOWN ? 2 : 1; c.upsample = n.kind == N_UP;
+      // variant 3's Downsample pads (0, 1, 0, 1) and convolves with padding 0 (pesser/model.py:66-70): taps from 2o
+      if (n.kind == N_DOWN && arch.variant == 3) c.s2_pad0 = 1;
       c.w = P(cv.w); c.K = cv.K;
       c.y = y.p; c.y_pitch = y.pitch; c.Cout = n.cout; c.B = B; c.pick_B = kPickBatch;
       c.Hout = Hl(n.level_out); c.Wout = Wl(n.level_out);
@@ -1242,7 +1354,8 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         // plan never takes otherwise (reference-fixture forwards off by 0.14)
         ConvArgs s = c;
         split_for(s);
-        if (conv_k32_pick(s) == 9) {
+        const int v = conv_k32_pick(s);
+        if (v == 9 || (c.s2_pad0 && v == 13)) {  // (13: the row-segment form of the bottom/right-padded conv)
           c = s;
           emit_conv(c, y);
         } else {
@@ -1271,11 +1384,11 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     // channels: the gn_finalize launch
     GnFin fin;
     if (toggles().gn_fusion && C <= 512 && C % G == 0 && nchunk <= 64) {
-      fin.part = stl; fin.G = G; fin.nchunk = nchunk; fin.n = (double)H * W * (C / G); fin.eps = 1e-5f;
+      fin.part = stl; fin.G = G; fin.nchunk = nchunk; fin.n = (double)H * W * (C / G); fin.eps = gn_eps;
       fin.gamma = P(lg.g); fin.beta = P(lg.b);
     } else {
       add("gn_finalize", 0, 8.0 * B * C, [=](hipStream_t st) {
-        return gn_finalize(xin, G, stl, 1e-5f, self->P(lg.g), self->P(lg.b), gsc, gsh, st);
+        return gn_finalize(xin, G, stl, gn_eps, self->P(lg.g), self->P(lg.b), gsc, gsh, st);
       });
     }
     (void)va;
@@ -1308,6 +1421,22 @@ extern "C" int dm_unet_param_count(const dm_unet_arch* arch, int* n_params) {
   if (rc) return rc;
   if (!n_params) { dm::set_error("n_params is null"); return DM_ERR_ARG; }
   *n_params = dm::count_params(*arch);
+  return DM_OK;
+}
+
+/* Test hook (tests/test_pesser_host.py; host only): the state_dict index of every tensor in the order the executor
+ * consumes them. Variant 3: dm::walk_order(); the other variants read the state_dict as it is registered. */
+extern "C" int dm_debug_unet_param_order(const dm_unet_arch* arch, int* order, int n) {
+  int rc = dm::validate_arch(arch);
+  if (rc) return rc;
+  if (!order || n != dm::count_params(*arch)) { dm::set_error("order: one slot per parameter tensor"); return DM_ERR_ARG; }
+  if (arch->variant == 3) {
+    const std::vector<int> w = dm::walk_order(*arch);
+    if ((int)w.size() != n) { dm::set_error("variant 3: parameter order table does not cover the state_dict"); return DM_ERR_STATE; }
+    for (int i = 0; i < n; ++i) order[i] = w[i];
+  } else {
+    for (int i = 0; i < n; ++i) order[i] = i;
+  }
   return DM_OK;
 }
 

@@ -9,6 +9,10 @@ the reference builds at sample_uncond.py:281-286 —
 crop offsets are int(round((H - size) / 2)), ToTensor divides uint8 by 255, Normalize is (x - 0.5) / 0.5.
 Parity of the resize against torchvision itself is unpinned (no torchvision here); for inputs already at
 img_size the chain is exact.
+
+`resize_square_normalize` is the chain of the reference's scripts/sample_sdedit.py:128-132,
+    Resize((img_size, img_size)) -> ToTensor() -> Normalize([0.5]*3, [0.5]*3)
+(both sides to img_size, the aspect ratio not kept), selected with ``ImageDir(..., transform=...)``.
 """
 import os
 from typing import List
@@ -46,14 +50,26 @@ def resize_center_crop_normalize(img, size: int) -> torch.Tensor:
     return (x - 0.5) / 0.5
 
 
-class ImageDir(torch.utils.data.Dataset):
-    """datasets/ImageDir.py:19-35 with the reconstruction transform built in."""
+def resize_square_normalize(img, size: int) -> torch.Tensor:
+    """PIL RGB image -> [3, size, size] float32 in [-1, 1], resized to size x size without keeping the aspect ratio
+    (sample_sdedit.py:128-132); PIL bilinear, a no-op when the image already has that size."""
+    from PIL import Image
+    if img.size != (size, size):
+        img = img.resize((size, size), Image.BILINEAR)
+    x = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).permute(2, 0, 1).float().div(255)
+    return (x - 0.5) / 0.5
 
-    def __init__(self, root: str, img_size: int):
+
+class ImageDir(torch.utils.data.Dataset):
+    """datasets/ImageDir.py:19-35 with the reconstruction transform built in (or `transform`, (PIL image, img_size)
+    -> tensor)."""
+
+    def __init__(self, root: str, img_size: int, transform=resize_center_crop_normalize):
         root = os.path.expanduser(root)
         if not os.path.isdir(root):
             raise ValueError(f'{root} is not a valid directory')
         self.img_size = img_size
+        self.transform = transform
         self.img_paths = extract_images(root)
 
     def __len__(self):
@@ -62,4 +78,4 @@ class ImageDir(torch.utils.data.Dataset):
     def __getitem__(self, item):
         from PIL import Image
         with Image.open(self.img_paths[item]) as im:
-            return resize_center_crop_normalize(im.convert('RGB'), self.img_size)
+            return self.transform(im.convert('RGB'), self.img_size)

@@ -5,6 +5,8 @@ byte parity with it is unpinned): a [B, C, H, W] tensor or a list of [C, H, W]
 images is tiled nrow per row with `padding` pixels of `pad_value` around every
 tile (a single image is returned as is, no padding); 1-channel images are
 replicated to RGB; float [0, 1] -> uint8 via x * 255 + 0.5 clamped and truncated.
+`normalize=True, value_range=(low, high)` clamps to the range and maps it to [0, 1] first, (x - low) /
+max(high - low, 1e-5), over the whole batch at once (make_grid's scale_each=False).
 """
 import struct
 import zlib
@@ -17,10 +19,14 @@ def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
 
 
-def make_grid(tensor, nrow: int = 8, padding: int = 2, pad_value: float = 0.0) -> torch.Tensor:
-    """torchvision/utils.py make_grid (0.16), normalize=False."""
+def make_grid(tensor, nrow: int = 8, padding: int = 2, pad_value: float = 0.0, normalize: bool = False,
+              value_range=None) -> torch.Tensor:
+    """torchvision/utils.py make_grid (0.16), scale_each=False."""
     if isinstance(tensor, (list, tuple)):
         tensor = torch.stack(list(tensor), dim=0)
+    if normalize:
+        low, high = value_range if value_range is not None else (float(tensor.min()), float(tensor.max()))
+        tensor = tensor.clone().clamp_(min=low, max=high).sub_(low).div_(max(high - low, 1e-5))
     if tensor.dim() == 2:
         tensor = tensor.unsqueeze(0)
     if tensor.dim() == 3:
@@ -54,10 +60,12 @@ def to_uint8(image: torch.Tensor) -> np.ndarray:
     return x.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).numpy()
 
 
-def save_image(image, path: str, nrow: int = 8, padding: int = 2, pad_value: float = 0.0):
+def save_image(image, path: str, nrow: int = 8, padding: int = 2, pad_value: float = 0.0, normalize: bool = False,
+               value_range=None):
     """torchvision/utils.py save_image (0.16): make_grid, then one 8-bit RGB PNG."""
-    if isinstance(image, (list, tuple)) or image.dim() == 4:
-        image = make_grid(image, nrow=nrow, padding=padding, pad_value=pad_value)
+    if isinstance(image, (list, tuple)) or image.dim() == 4 or normalize:
+        image = make_grid(image, nrow=nrow, padding=padding, pad_value=pad_value, normalize=normalize,
+                          value_range=value_range)
     rgb = to_uint8(image)
     h, w, _ = rgb.shape
     raw = b''.join(b'\x00' + rgb[y].tobytes() for y in range(h))

@@ -55,10 +55,13 @@ def synthetic_state_dict(state_dict_like: Dict[str, torch.Tensor], seed: int = 0
 
 def init_synthetic_(model: torch.nn.Module, seed: int = 0):
     """Load the synthetic weights into `model` in place; returns their sha256. An MDTv2 (a state_dict with
-    ``relative_position_index`` buffers) takes synthetic_mdt_state_dict."""
+    ``relative_position_index`` buffers) takes synthetic_mdt_state_dict, the pesser DDPM UNet (``temb.dense.*`` keys)
+    synthetic_pesser_state_dict."""
     ref = model.state_dict()
     if any(k.endswith('relative_position_index') for k in ref):
         sd = synthetic_mdt_state_dict(ref, seed)
+    elif 'temb.dense.0.weight' in ref:
+        sd = synthetic_pesser_state_dict(ref, seed)
     else:
         sd = synthetic_state_dict(ref, seed)
     model.load_state_dict(sd)
@@ -93,6 +96,33 @@ def synthetic_mdt_state_dict(state_dict_like: Dict[str, torch.Tensor], seed: int
             out[name] = torch.from_numpy(rng.standard_normal(tuple(ref.shape), dtype=np.float32))
         elif name == 'decoder_pos_embed' or (name.endswith('adaLN_modulation.1.bias') and 'blocks.' in name):
             out[name] = torch.from_numpy((rng.random(tuple(ref.shape), dtype=np.float32) * 2.0 - 1.0))
+        else:
+            out[name] = syn[name]
+    return out
+
+
+def synthetic_pesser_state_dict(state_dict_like: Dict[str, torch.Tensor], seed: int = 0) -> Dict[str, torch.Tensor]:
+    """Synthetic weights over a pesser DDPM UNet state_dict (models/pesser/model.py): synthetic_state_dict, then from
+    a second PCG64 stream (seed + 1), in key order: GroupNorm (``norm*``) weight ~ U(0.5, 1.5) and bias ~ U(-0.5, 0.5)
+    (an affine that is not the identity, so a GroupNorm applied with the wrong statistics or eps shows), every other
+    bias ~ U(-0.1, 0.1), and the attention blocks' ``q`` and ``k`` conv weights x 4 (consuming no draws): with the
+    recipe's fan-in bound the scores are nearly flat and uniform attention would move the output by 0.03 only; x 4
+    makes the softmax decide it (x 8 raises the reference's own float32 error to 1.6e-4)."""
+    syn = synthetic_state_dict(state_dict_like, seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    out = {}
+    for name, ref in state_dict_like.items():
+        shape = tuple(ref.shape)
+        mod, _, leaf = name.rpartition('.')
+        is_norm = mod.rpartition('.')[2].startswith('norm')
+        if len(shape) == 1 and is_norm:
+            u = rng.random(shape, dtype=np.float32)
+            out[name] = torch.from_numpy(u + np.float32(0.5) if leaf == 'weight' else u - np.float32(0.5))
+        elif len(shape) == 1 and leaf == 'bias':
+            u = rng.random(shape, dtype=np.float32)
+            out[name] = torch.from_numpy((u * np.float32(2.0) - np.float32(1.0)) * np.float32(0.1))
+        elif leaf == 'weight' and mod.rpartition('.')[2] in ('q', 'k'):
+            out[name] = syn[name] * 4.0
         else:
             out[name] = syn[name]
     return out

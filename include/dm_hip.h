@@ -70,7 +70,11 @@ typedef struct dm_unet_arch {
   int n_heads;          /* variant 0: heads of the stage attention blocks */
   /* variant 0: models/unet.py UNet (time-embedding add after conv1, conv down/upsample);
    * variant 1: models/unet_categorial_adagn.py UNetCategorialAdaGN (AdaGN before conv2,
-   *            heads = C / attn_head_dims, ResBlock up/down when resblock_updown, class embedding) */
+   *            heads = C / attn_head_dims, ResBlock up/down when resblock_updown, class embedding);
+   * variant 3: models/pesser/model.py Model (variant 0 with GroupNorm eps 1e-6, a Downsample padded at the
+   *            bottom / right only, one attention head of C channels, and the parameters in that module's
+   *            state_dict order). dim = ch, dim_mults = ch_mult, use_attn[l] = (resolution >> l) in
+   *            attn_resolutions; the other fields are ignored. */
   int variant;
   int num_classes;      /* variants 1, 2: class-embedding rows (0 = no class embedding) */
   int attn_head_dims;   /* variant 1; variant 2: num_head_channels (<= 0: use n_heads / n_heads_up) */
