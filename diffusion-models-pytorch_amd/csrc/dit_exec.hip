@@ -28,6 +28,7 @@
 #include "dm_common.h"
 #include "dm_kernels.h"
 #include "plan.h"
+#include "exec_core.h"
 
 namespace dm {
 
@@ -88,36 +89,25 @@ int mdt_validate(const dm_mdt_arch* a) {
 
 // DiT and MDTv2 share this model: MDT (mdt true) adds the per-block bias tables, the skip_linear weights, the
 // decoder position table and the en_in / en_out / de topology of build_plan.
-struct DiTModel {
+struct DiTModel : ExecNet {
   dm_dit_arch arch;
   bool mdt = false;
   int half_depth = 0, decode_layer = 0;   // MDT: blocks = en_inblocks, en_outblocks, de_blocks (the executed ones)
   int W = 0, bias_hs = 0;                 // MDT: token grid width, floats per head of a transposed bias table
   size_t dpos = 0;                        // MDT: decoder_pos_embed
-  float* arena = nullptr;
-  size_t arena_floats = 0;
   int D = 0, T = 0, OC = 0, PP = 0, ada_total = 0;
   size_t pos, xw, xb, tw1, tb1, tw2, tb2, ytab, freqs, ada_w, ada_b, fin_w, fin_b;
+  int n_freqs = 128;
   bool freqs_set = false;
   std::vector<BlockP> blocks;
-  // Arithmetic of the token GEMMs (qkv, attention, proj, fc1, fc2, final): 2 = fp16x2 split (gemm.hip
-  // SPLIT; default unless DM_CONV_MATH=fp32|bf16x3), 0 = fp32 MFMA. A forward that raises range_flag
-  // (an operand beyond the fp16 range) runs again in fp32; the next forward is fp16x2 again (plans cached
-  // per (B, arithmetic)). Deferred mode: dm_dit_range_poll sets `fallback` for the caller's re-run,
-  // dm_dit_range_fallback clears it. `math` is the arithmetic of the plan being built (set by get_plan).
-  int base_math = conv_math_from_env() == 2 ? 2 : 0;
-  bool fallback = false;
-  long range_fallbacks = 0;
-  int math = base_math;
-  int run_math() const { return base_math == 2 && fallback ? 0 : base_math; }
-  bool range_check = toggles().range_check;
-  int* range_flag = nullptr;
-  int* range_flag_host = nullptr;
-  bool range_deferred = false;  // dm_dit_set_range_deferred / dm_dit_range_poll, as for the UNet
-  std::map<const float*, int> w_exp;
-  // fp16x2 fragment images of the token-GEMM weights (split_conv_weights, taps 1), built once: those GEMMs
-  // run linear_k32 (K = 32 MFMA steps, no per-load split of the weights)
-  std::map<const float*, void*> split_w;
+  // Arithmetic of the token GEMMs (qkv, attention, proj, fc1, fc2, final), ExecNet's: 2 = fp16x2 split (gemm.hip
+  // SPLIT; default unless DM_CONV_MATH=fp32|bf16x3), 0 = fp32 MFMA, which is also the range fallback. split_w holds
+  // the fp16x2 fragment images of the token-GEMM weights (split_conv_weights, taps 1), built once: those GEMMs run
+  // linear_k32 (K = 32 MFMA steps, no per-load split of the weights)
+  DiTModel() {
+    base_math = conv_math = conv_math_from_env() == 2 ? 2 : 0;
+    fallback_math = 0;
+  }
   bool linear_k32_on = true;
   // linear_k32's split-K tail (GemmArgs::sk_*): one 64-KB slab per resident block and one arrival counter per
   // tile, zeroed once (each tile's reducing block resets its counter); forwards of this model's plans are
@@ -136,21 +126,14 @@ struct DiTModel {
     float* out = nullptr;
   };
   PlanCache<Plan> plans;  // LRU over B, scratch from one pool
-  size_t split_bytes = 0;  // device bytes of the split_w copies
 
-  float* P(size_t off) const { return arena + off; }
   ~DiTModel() {
-    plans.clear();
-    for (auto& kv : split_w) (void)hipFree(kv.second);
-    if (range_flag) (void)hipFree(range_flag);
     if (sk_ws) (void)hipFree(sk_ws);
     if (sk_cnt) (void)hipFree(sk_cnt);
-    if (range_flag_host) (void)hipHostFree(range_flag_host);
-    if (arena) (void)hipFree(arena);
   }
   int build_plan(Plan& pl, int B);
   int get_plan(int B, int m, Plan** out) {
-    math = m;
+    conv_math = m;
     return plans.get([&](const Plan& p) { return p.B == B && p.math == m; }, [&](Plan& p) { return build_plan(p, B); },
                      out);
   }
@@ -297,18 +280,14 @@ int DiTModel::build_plan(Plan& pl, int B) {
   ToggleScope scope(pl.toggles);
   pl.graph_enabled = toggles().graph;
   pl.B = B;
-  pl.math = math;
+  pl.math = conv_math;
   const dm_dit_arch& a = arch;
   const int p = a.patch_size, C = a.in_channels, S = a.input_size, Hm = a.mlp_hidden;
   const int heads = a.num_heads, Dh = D / heads;
   const long M = (long)B * T;
   DM_REQUIRE((long)B * heads <= 65535, "batch * heads too large for one attention launch");
 
-  if (!range_flag) {
-    DM_CHECK_HIP(hipMalloc(&range_flag, sizeof(int)));
-    DM_CHECK_HIP(hipMemset(range_flag, 0, sizeof(int)));
-    DM_CHECK_HIP(hipHostMalloc(&range_flag_host, sizeof(int)));
-  }
+  if (const int rcf = ensure_range_flag()) return rcf;
   if (!sk_ws && toggles().lin_sk && linear_k32_slots() > 0) {
     const int slots = linear_k32_slots();
     DM_CHECK_HIP(hipMalloc(&sk_ws, (size_t)slots * 65536));
@@ -405,30 +384,28 @@ int DiTModel::build_plan(Plan& pl, int B) {
     flush_stats();
     add_gemm(g);
   };
-  // fp16x2 operand exponents (unet_exec.hip split_gemm): weights by max |w|, activations fixed (2^6 for
+  // fp16x2 operand exponents (ExecNet::split_gemm): weights by max |w|, activations fixed (2^6 for
   // LayerNorm-modulated tokens, q, k, v, attention and MLP outputs; 2^14 for softmax rows)
   auto split = [&](GemmArgs& g, int ea, size_t w, size_t wn, int eb_act) {
-    if (math != 2) return;
-    int eb = eb_act;
-    if (wn) {
-      auto it = w_exp.find(P(w));
-      if (it == w_exp.end()) it = w_exp.emplace(P(w), split_weight_exponent(P(w), wn)).first;
-      eb = it->second;
-    }
-    g.split = 2; g.split_ea = ea; g.split_eb = eb; g.range_flag = range_flag;
+    split_gemm(g, ea, wn ? P(w) : nullptr, wn, eb_act);
+    if (conv_math != 2) return;
     // static weight [N][K]: pre-split once for linear_k32 (the gemm.hip path stays the fallback)
     if (wn && linear_k32_on && g.K % 64 == 0 && g.N % 4 == 0) {
-      const float* wp = P(w);
-      auto it = split_w.find(wp);
+      const auto key = std::make_pair((const float*)P(w), 2);
+      auto it = split_w.find(key);
       if (it == split_w.end()) {
         void* buf = nullptr;
         const size_t nb = split_conv_weights_bytes(1, g.N, g.K, 2);
-        if (hipMalloc(&buf, nb) != hipSuccess) return;
-        if (split_conv_weights(wp, 1, g.N, g.K, g.K, 1, 2, buf, nullptr) != DM_OK || hipDeviceSynchronize() != hipSuccess) {
+        if (hipMalloc(&buf, nb) != hipSuccess) {
+          (void)hipGetLastError();
+          return;
+        }
+        if (split_conv_weights(key.first, 1, g.N, g.K, g.K, 1, 2, buf, nullptr) != DM_OK ||
+            hipDeviceSynchronize() != hipSuccess) {
           (void)hipFree(buf);
           return;
         }
-        it = split_w.emplace(wp, buf).first;
+        it = split_w.emplace(key, buf).first;
         split_bytes += nb;
       }
       g.ws = it->second;
@@ -508,7 +485,7 @@ int DiTModel::build_plan(Plan& pl, int B) {
     split(gq, 6, bp.qkv_w, (size_t)3 * D * D, 0);
     // flash attention (attention.hip attn_flash_kernel): the qkv GEMM's epilogue writes q * d^-1/2, k, v as
     // the fp16x2 operand planes (over the qkv buffer: same bytes), S never leaves the CU
-    const bool flash = math == 2 && gq.ws && attn_flash_ok(T, Dh) && toggles().attn != kAttnUnfused &&
+    const bool flash = conv_math == 2 && gq.ws && attn_flash_ok(T, Dh) && toggles().attn != kAttnUnfused &&
                        (!biased || attn_flash_bias_ok(T, W));
     _Float16* planes = reinterpret_cast<_Float16*>(qkv);
     const size_t plane_n = (size_t)M * D * 2;   // fp16 elements of one operand's two planes
@@ -638,12 +615,7 @@ int DiTModel::build_plan(Plan& pl, int B) {
       GemmArgs g = linear(A, D, M, bp.skip_w + woff, bias ? bp.skip_b : kNone, D, D, C, D);
       g.ldb = 2 * D;
       g.res = res; g.ld_res = D;
-      if (math == 2) {   // one exponent for both halves: that of the whole [D][2D] matrix
-        auto it = w_exp.find(P(bp.skip_w));
-        if (it == w_exp.end())
-          it = w_exp.emplace(P(bp.skip_w), split_weight_exponent(P(bp.skip_w), (size_t)D * 2 * D)).first;
-        g.split = 2; g.split_ea = 6; g.split_eb = it->second; g.range_flag = range_flag;
-      }
+      split_gemm(g, 6, P(bp.skip_w), (size_t)D * 2 * D);  // one exponent for both halves: the whole [D][2D] matrix's
       add_gemm(g);
     };
     half(cur, 0, true, nullptr, Ob);
@@ -718,162 +690,68 @@ extern "C" int dm_dit_create(const dm_dit_arch* arch, const float* const* params
   return DM_OK;
 }
 
-extern "C" int dm_dit_forward(dm_dit* h, const float* x, const int64_t* t, const int64_t* y, int B, float* out,
-                              void* stream) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
+// dm_dit_forward and dm_mdt_forward
+static int dit_forward(dm::DiTModel* m, const float* x, const int64_t* t, const int64_t* y, int B, float* out,
+                       hipStream_t st) {
+  DM_ABI_MODEL(m);
   if (!x || !t || !out) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   if (B <= 0) { dm::set_error("empty batch"); return DM_ERR_ARG; }
   if (static_cast<const void*>(out) == static_cast<const void*>(x)) {
     dm::set_error("out must not alias x");
     return DM_ERR_ARG;
   }
-  dm::DiTModel* m = h->m;
-  hipStream_t st = (hipStream_t)stream;
   const int S = m->arch.input_size;
   const size_t nx = (size_t)B * m->arch.in_channels * S * S, no = (size_t)B * m->OC * S * S;
-  // at most two passes: the caller's arithmetic, then (an fp16x2 operand beyond the fp16 range) fp32
-  if (const int rco = m->plans.pool->order(st)) return rco;
-  // every exit after order() records the completion event, so a later forward on another stream waits for
-  // whatever this one enqueued over the shared slab, even when it failed part way
-  const int rc_body = [&]() -> int {
-    for (int math = m->run_math();;) {
-      dm::DiTModel::Plan* plp = nullptr;
-      const int rc0 = m->get_plan(B, math, &plp);
-      if (rc0) return rc0;
-      auto& pl = *plp;
-      DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
-      DM_CHECK_HIP(hipMemcpyAsync(pl.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-      if (y)
-        DM_CHECK_HIP(hipMemcpyAsync(pl.y, y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-      else
-        DM_CHECK_HIP(hipMemsetAsync(pl.y, 0xff, (size_t)B * sizeof(int64_t), st));  // -1: the null class
-      const int rc = pl.run(st);
-      if (rc) return rc;
-      DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
-      if (math != 2 || !m->range_check || m->range_deferred) break;
-      DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      DM_CHECK_HIP(hipStreamSynchronize(st));
-      if (!*m->range_flag_host) break;
-      DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-      m->range_fallbacks++;
-      math = 0;
-    }
-    return DM_OK;
-  }();
-  const int rc_mark = m->plans.pool->mark(st);
-  return rc_body ? rc_body : rc_mark;
+  using Plan = dm::DiTModel::Plan;
+  return dm::run_forward(
+      *m, st, [&](int math, Plan** pl) { return m->get_plan(B, math, pl); },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
+        DM_CHECK_HIP(hipMemcpyAsync(pl.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        if (y)
+          DM_CHECK_HIP(hipMemcpyAsync(pl.y, y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        else
+          DM_CHECK_HIP(hipMemsetAsync(pl.y, 0xff, (size_t)B * sizeof(int64_t), st));  // -1: the null class
+        return DM_OK;
+      },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DM_OK;
+      });
 }
 
+extern "C" int dm_dit_forward(dm_dit* h, const float* x, const int64_t* t, const int64_t* y, int B, float* out,
+                              void* stream) {
+  return dit_forward(dm::model_of(h), x, t, y, B, out, (hipStream_t)stream);
+}
 extern "C" int dm_dit_set_range_deferred(dm_dit* h, int deferred) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  h->m->range_deferred = deferred != 0;
-  return DM_OK;
+  return dm::abi_set_range_deferred(dm::model_of(h), deferred);
 }
-
 extern "C" int dm_dit_range_poll(dm_dit* h, void* stream, int* flagged) {
-  if (!h || !h->m || !flagged) { dm::set_error("null model / argument"); return DM_ERR_STATE; }
-  dm::DiTModel* m = h->m;
-  *flagged = 0;
-  if (!m->range_flag) return DM_OK;
-  hipStream_t st = (hipStream_t)stream;
-  DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  DM_CHECK_HIP(hipStreamSynchronize(st));
-  if (*m->range_flag_host) {
-    DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-    *flagged = 1;
-    if (m->base_math == 2) {  // the caller re-runs what it computed since the last poll: in fp32
-      m->fallback = true;
-      m->range_fallbacks++;
-    }
-  }
-  return DM_OK;
+  return dm::abi_range_poll(dm::model_of(h), (hipStream_t)stream, flagged);
 }
-
-extern "C" int dm_dit_range_fallback(dm_dit* h, int on) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  h->m->fallback = on != 0;
-  return DM_OK;
-}
-
+extern "C" int dm_dit_range_fallback(dm_dit* h, int on) { return dm::abi_range_fallback(dm::model_of(h), on); }
 extern "C" int dm_dit_range_stats(const dm_dit* h, int64_t* fallbacks, int* active) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (fallbacks) *fallbacks = h->m->range_fallbacks;
-  if (active) *active = h->m->run_math();
-  return DM_OK;
+  return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
 }
-
-extern "C" int dm_dit_set_math(dm_dit* h, int kind) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (kind != 0 && kind != DM_SPLIT_FP16X2) { dm::set_error("DiT math must be 0 (fp32) or DM_SPLIT_FP16X2"); return DM_ERR_ARG; }
-  h->m->fallback = false;
-  if (kind != h->m->base_math) {
-    h->m->base_math = kind;
-    h->m->plans.clear();
-  }
-  return DM_OK;
-}
-
-extern "C" int dm_dit_get_math(const dm_dit* h, int* kind) {
-  if (!h || !h->m || !kind) { dm::set_error("null model"); return DM_ERR_STATE; }
-  *kind = h->m->base_math;
-  return DM_OK;
-}
-
+extern "C" int dm_dit_set_math(dm_dit* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false); }
+extern "C" int dm_dit_get_math(const dm_dit* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
 extern "C" int dm_dit_set_time_freqs(dm_dit* h, const float* freqs, int n, void* stream) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (!freqs) {
-    h->m->freqs_set = false;
-    h->m->plans.invalidate_graphs();
-    return DM_OK;
-  }
-  if (n != 128) { dm::set_error("time frequency table must have 128 entries"); return DM_ERR_ARG; }
-  DM_CHECK_HIP(hipMemcpyAsync(h->m->P(h->m->freqs), freqs, 128 * sizeof(float), hipMemcpyDefault,
-                              (hipStream_t)stream));
-  h->m->freqs_set = true;
-  h->m->plans.invalidate_graphs();
-  return DM_OK;
+  return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);
 }
-
-extern "C" int dm_dit_profile(dm_dit* h, int enable) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (!h->m->plans.current()) { dm::set_error("no plan yet: run dm_dit_forward once first"); return DM_ERR_STATE; }
-  h->m->plans.current()->profile_enable(enable);
-  return DM_OK;
-}
-
-extern "C" int dm_dit_profile_count(dm_dit* h, int* n_ops) {
-  if (!h || !h->m || !h->m->plans.current() || !n_ops) { dm::set_error("null model / no plan"); return DM_ERR_STATE; }
-  *n_ops = (int)h->m->plans.current()->ops.size();
-  return DM_OK;
-}
-
+extern "C" int dm_dit_profile(dm_dit* h, int enable) { return dm::abi_profile(dm::model_of(h), enable); }
+extern "C" int dm_dit_profile_count(dm_dit* h, int* n_ops) { return dm::abi_profile_count(dm::model_of(h), n_ops); }
 extern "C" int dm_dit_profile_get(dm_dit* h, int i, char* label, int label_len, double* flops, double* bytes,
                                   double* ms_total, int64_t* launches) {
-  if (!h || !h->m || !h->m->plans.current()) { dm::set_error("null model / no plan"); return DM_ERR_STATE; }
-  return h->m->plans.current()->profile_get(i, label, label_len, flops, bytes, ms_total, launches);
+  return dm::abi_profile_get(dm::model_of(h), i, label, label_len, flops, bytes, ms_total, launches);
 }
-
 extern "C" int dm_dit_memory(const dm_dit* h, int64_t* weight_bytes, int64_t* workspace_bytes) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  // the fp32 arena plus the pre-split fp16x2 copies of the token-GEMM weights (as dm_unet_memory counts them)
-  if (weight_bytes) *weight_bytes = (int64_t)(h->m->arena_floats * sizeof(float) + h->m->split_bytes);
-  if (workspace_bytes) *workspace_bytes = (int64_t)h->m->plans.pool->bytes();
-  return DM_OK;
+  return dm::abi_memory(dm::model_of(h), weight_bytes, workspace_bytes);
 }
-
 extern "C" int dm_dit_plan_stats(const dm_dit* h, int64_t* builds, int* cached) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (builds) *builds = h->m->plans.builds;
-  if (cached) *cached = (int)h->m->plans.plans.size();
-  return DM_OK;
+  return dm::abi_plan_stats(dm::model_of(h), builds, cached);
 }
-
-extern "C" void dm_dit_destroy(dm_dit* h) {
-  if (!h) return;
-  (void)hipDeviceSynchronize();
-  delete h->m;
-  delete h;
-}
+extern "C" void dm_dit_destroy(dm_dit* h) { dm::abi_destroy(h); }
 
 // ===========================================================================
 // C ABI: MDTv2 (the same model object and the same calls as dm_dit_*)
@@ -901,33 +779,35 @@ extern "C" int dm_mdt_create(const dm_mdt_arch* arch, const float* const* params
   return DM_OK;
 }
 
-#define DM_MDT_FWD(h) dm_dit d_{(h) ? (h)->m : nullptr}
-
 extern "C" int dm_mdt_forward(dm_mdt* h, const float* x, const int64_t* t, const int64_t* y, int B, float* out,
                               void* stream) {
-  DM_MDT_FWD(h);
-  return dm_dit_forward(&d_, x, t, y, B, out, stream);
+  return dit_forward(dm::model_of(h), x, t, y, B, out, (hipStream_t)stream);
 }
-extern "C" int dm_mdt_set_range_deferred(dm_mdt* h, int deferred) { DM_MDT_FWD(h); return dm_dit_set_range_deferred(&d_, deferred); }
-extern "C" int dm_mdt_range_poll(dm_mdt* h, void* stream, int* flagged) { DM_MDT_FWD(h); return dm_dit_range_poll(&d_, stream, flagged); }
-extern "C" int dm_mdt_range_fallback(dm_mdt* h, int on) { DM_MDT_FWD(h); return dm_dit_range_fallback(&d_, on); }
-extern "C" int dm_mdt_range_stats(const dm_mdt* h, int64_t* fallbacks, int* active) { DM_MDT_FWD(h); return dm_dit_range_stats(&d_, fallbacks, active); }
-extern "C" int dm_mdt_set_math(dm_mdt* h, int kind) { DM_MDT_FWD(h); return dm_dit_set_math(&d_, kind); }
-extern "C" int dm_mdt_get_math(const dm_mdt* h, int* kind) { DM_MDT_FWD(h); return dm_dit_get_math(&d_, kind); }
-extern "C" int dm_mdt_set_time_freqs(dm_mdt* h, const float* freqs, int n, void* stream) { DM_MDT_FWD(h); return dm_dit_set_time_freqs(&d_, freqs, n, stream); }
-extern "C" int dm_mdt_profile(dm_mdt* h, int enable) { DM_MDT_FWD(h); return dm_dit_profile(&d_, enable); }
-extern "C" int dm_mdt_profile_count(dm_mdt* h, int* n_ops) { DM_MDT_FWD(h); return dm_dit_profile_count(&d_, n_ops); }
+extern "C" int dm_mdt_set_range_deferred(dm_mdt* h, int deferred) {
+  return dm::abi_set_range_deferred(dm::model_of(h), deferred);
+}
+extern "C" int dm_mdt_range_poll(dm_mdt* h, void* stream, int* flagged) {
+  return dm::abi_range_poll(dm::model_of(h), (hipStream_t)stream, flagged);
+}
+extern "C" int dm_mdt_range_fallback(dm_mdt* h, int on) { return dm::abi_range_fallback(dm::model_of(h), on); }
+extern "C" int dm_mdt_range_stats(const dm_mdt* h, int64_t* fallbacks, int* active) {
+  return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
+}
+extern "C" int dm_mdt_set_math(dm_mdt* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false); }
+extern "C" int dm_mdt_get_math(const dm_mdt* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
+extern "C" int dm_mdt_set_time_freqs(dm_mdt* h, const float* freqs, int n, void* stream) {
+  return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);
+}
+extern "C" int dm_mdt_profile(dm_mdt* h, int enable) { return dm::abi_profile(dm::model_of(h), enable); }
+extern "C" int dm_mdt_profile_count(dm_mdt* h, int* n_ops) { return dm::abi_profile_count(dm::model_of(h), n_ops); }
 extern "C" int dm_mdt_profile_get(dm_mdt* h, int i, char* label, int label_len, double* flops, double* bytes,
                                   double* ms_total, int64_t* launches) {
-  DM_MDT_FWD(h);
-  return dm_dit_profile_get(&d_, i, label, label_len, flops, bytes, ms_total, launches);
+  return dm::abi_profile_get(dm::model_of(h), i, label, label_len, flops, bytes, ms_total, launches);
 }
-extern "C" int dm_mdt_memory(const dm_mdt* h, int64_t* weight_bytes, int64_t* workspace_bytes) { DM_MDT_FWD(h); return dm_dit_memory(&d_, weight_bytes, workspace_bytes); }
-extern "C" int dm_mdt_plan_stats(const dm_mdt* h, int64_t* builds, int* cached) { DM_MDT_FWD(h); return dm_dit_plan_stats(&d_, builds, cached); }
-
-extern "C" void dm_mdt_destroy(dm_mdt* h) {
-  if (!h) return;
-  (void)hipDeviceSynchronize();
-  delete h->m;
-  delete h;
+extern "C" int dm_mdt_memory(const dm_mdt* h, int64_t* weight_bytes, int64_t* workspace_bytes) {
+  return dm::abi_memory(dm::model_of(h), weight_bytes, workspace_bytes);
 }
+extern "C" int dm_mdt_plan_stats(const dm_mdt* h, int64_t* builds, int* cached) {
+  return dm::abi_plan_stats(dm::model_of(h), builds, cached);
+}
+extern "C" void dm_mdt_destroy(dm_mdt* h) { dm::abi_destroy(h); }

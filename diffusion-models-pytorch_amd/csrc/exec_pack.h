@@ -1,8 +1,7 @@
-// Create-time helpers shared by the model executors (unet_exec.hip, vae_exec.hip): reading the caller's
-// state_dict tensors in registration order, packing them into one library-owned device arena, and the fp16x2
-// operand exponents of the attention GEMMs.
+// Create-time helpers shared by the conv-net executors (the UNet and both VAE networks): reading the caller's
+// state_dict tensors in registration order and packing them into one library-owned device arena (ExecNet::arena,
+// exec_core.h).
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
@@ -92,26 +91,6 @@ inline int run_pack_jobs(const Packer& pk, float* arena, hipStream_t st) {
     }
   }
   return DM_OK;
-}
-
-// fp16x2 attention GEMMs (gemm.hip SPLIT): A scaled by 2^ea, B by the weight's exponent (max |w| *
-// 2^eb in [2^13, 2^14); cached in w_exp) or, for an activation B, 2^eb_act. Activations use fixed exponents that keep
-// their low fp16 pieces normal down to ~2^-8 while leaving headroom to 65504 / 2^e (the range flag
-// catches the rest): GroupNorm'd inputs, q, k, v and the attention output 2^6, softmax rows (<= 1) 2^14.
-inline void split_gemm_args(GemmArgs& g, int conv_math, std::map<const float*, int>& w_exp, int* range_flag, int ea,
-                            const float* weight, size_t weight_n, int eb_act) {
-  g.split = 0;
-  if (conv_math != 2) return;
-  int eb = eb_act;
-  if (weight) {
-    auto it = w_exp.find(weight);
-    if (it == w_exp.end()) it = w_exp.emplace(weight, split_weight_exponent(weight, weight_n)).first;
-    eb = it->second;
-  }
-  g.split = 2;
-  g.split_ea = ea;
-  g.split_eb = eb;
-  g.range_flag = range_flag;
 }
 
 }  // namespace dm

@@ -24,6 +24,7 @@
 #include "dm_kernels.h"
 #include "plan.h"
 #include "exec_pack.h"
+#include "exec_core.h"
 
 namespace dm {
 
@@ -74,14 +75,14 @@ struct Node {
 
 }  // namespace
 
-struct UNetModel {
+// (the weight arena, the arithmetic -- fallback bf16x3 -- and the split / Winograd weights: ExecNet, exec_core.h)
+struct UNetModel : ExecNet {
   dm_unet_arch arch;
-  float* arena = nullptr;
-  size_t arena_floats = 0;
   // packed parameters (offsets into arena)
   size_t te_w1, te_b1, te_w2, te_b2;
-  size_t te_freqs;            // [dim/2] sinusoid frequencies
-  bool te_freqs_set = false;  // host table installed (else computed on device)
+  size_t freqs;            // [n_freqs = dim/2] sinusoid frequencies
+  int n_freqs = 0;
+  bool freqs_set = false;  // host table installed (else computed on device)
   size_t class_embed = 0;     // variants 1, 2: [num_classes][4 dim]
   bool has_class = false;
   size_t first_w, first_b;
@@ -109,28 +110,6 @@ struct UNetModel {
   };
   PlanCache<Plan> plans;
   float* last_packed = nullptr;  // last conv weights as [9][Cin][CO] (small_out_pack), made at the first build
-  // Split copies of the halo-patch conv weights (conv_patch3.hip), made at the first plan build.
-  // base_math: the arithmetic the caller chose -- 2 fp16x2 (default), 3 bf16x3, 0 fp32 MFMA kernels
-  // (DM_CONV_MATH=fp16x2|bf16x3|fp32). fp16x2 convs raise range_flag on an activation beyond the fp16 range;
-  // that forward then runs again in bf16x3 and the next one is fp16x2 again (not sticky: plans are cached
-  // per (shape, arithmetic)). In deferred mode the caller's re-run of a flagged loop runs in bf16x3 while
-  // `fallback` is set (dm_unet_range_poll sets it, dm_unet_range_fallback clears it). DM_RANGE_CHECK=0
-  // skips the check and its sync. conv_math is the arithmetic of the plan being built (set by get_plan).
-  int base_math = conv_math_from_env();
-  bool fallback = false;
-  int conv_math = base_math;
-  int run_math() const { return base_math == 2 && fallback ? 3 : base_math; }
-  bool range_check = toggles().range_check;
-  int* range_flag = nullptr;       // device
-  int* range_flag_host = nullptr;  // pinned
-  // Deferred mode (dm_unet_set_range_deferred): forwards neither read the flag nor sync; the caller
-  // polls it once per sampling loop (dm_unet_range_poll) and re-runs the loop if it was raised.
-  bool range_deferred = false;
-  long range_fallbacks = 0;   // forwards / loops re-run in bf16x3 (dm_unet_range_stats)
-  std::map<std::pair<const float*, int>, void*> split_w;
-  std::map<std::pair<const float*, int>, void*> wino_w;  // Winograd F(2,3) weights (per shortcut fold) of its convs
-  size_t split_bytes = 0;
-  void split_for(ConvArgs& c);
   // folded single-head attention blocks (attn_block.hip): per block's qkv weights, the fp32 products At, w,
   // Wg, cb and the fp16x2 fragment images of At and Wg' (Wg with permuted columns), made at the first fp16x2
   // plan build
@@ -138,12 +117,12 @@ struct UNetModel {
   std::map<size_t, FoldW> folds;
   std::vector<void*> fold_mem;
   const FoldW* fold_for(const AttnP& p);
-  // fp16x2 GEMMs (attention): operand exponents; weights by max |w| (cached), activations fixed
-  std::map<const float*, int> w_exp;
-  void split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act = 0);
 
-  float* P(size_t off) const { return arena + off; }
-  ~UNetModel();
+  UNetModel() { wino_small = true; }
+  ~UNetModel() {
+    for (void* q : fold_mem) (void)hipFree(q);
+    if (last_packed) (void)hipFree(last_packed);
+  }
   int build_plan(Plan& pl, int B, int H, int W);
   int get_plan(int B, int H, int W, int math, Plan** out) {
     conv_math = math;
@@ -151,98 +130,6 @@ struct UNetModel {
                      [&](Plan& p) { return build_plan(p, B, H, W); }, out);
   }
 };
-
-UNetModel::~UNetModel() {
-  plans.clear();
-  for (void* q : fold_mem) (void)hipFree(q);
-  if (last_packed) (void)hipFree(last_packed);
-  for (auto& kv : split_w) (void)hipFree(kv.second);
-  for (auto& kv : wino_w) (void)hipFree(kv.second);
-  if (range_flag) (void)hipFree(range_flag);
-  if (range_flag_host) (void)hipHostFree(range_flag_host);
-  if (arena) (void)hipFree(arena);
-}
-
-// The split count of the Winograd kernel on a 4 x 4 map, 0 where the plan keeps the direct kernel: 4 splits when a
-// split has >= 12 K steps of 32 channels (maybe_split below; split_for attaches the Winograd weights to those only)
-static int wino_small_ks(const ConvArgs& c) {
-  if (c.Hout != 4 || c.Wout != 4) return 0;
-  const int ks = std::min(4, c.Cin1 / 32);
-  return ks >= 2 && (3 * (c.Cin1 / 32) + c.Cin2 / 64) / ks >= 12 ? ks : 0;
-}
-
-// Attach the split copy of a halo-patch conv's packed weights (none: the conv stays on the fp32
-// kernels).
-void UNetModel::split_for(ConvArgs& c) {
-  c.ws = nullptr;
-  c.ws_np = 0;
-  c.ws_rowscale = nullptr;
-  c.range_flag = nullptr;
-  // a bottom/right-padded stride-2 conv (variant 3's Downsample) that conv_split_eligible turns down also gets split
-  // weights when conv_k32's stride-2 tiles would run it given them (VaeNet::split_for, vae_blocks.h)
-  bool s2seg = false;
-  if (conv_math == 2 && c.s2_pad0 && c.stride == 2 && c.taps == 9) {
-    ConvArgs t = c;
-    t.ws = reinterpret_cast<const void*>(16);  // placeholders: the shape checks only
-    t.ws_np = 2;
-    t.ws_rowscale = reinterpret_cast<const float*>(16);
-    const int v = conv_k32_pick(t);
-    s2seg = v == 9 || v == 13;
-  }
-  if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)) || s2seg)) return;
-  if ((c.taps == 1 || c.stride == 2) && conv_math != 2) return;  // the split 1x1 / stride-2 paths are fp16x2 only
-  const int nmat = c.upsample == 2 ? 4 : 1;
-  const int ntap = c.upsample == 2 ? 4 : c.taps;
-  auto key = std::make_pair(c.w, conv_math);
-  auto it = split_w.find(key);
-  void* p = nullptr;
-  if (it != split_w.end()) {
-    p = it->second;
-  } else {
-    const size_t nb = split_conv_weights_bytes(nmat, c.Cout, c.K, conv_math);
-    if (hipMalloc(&p, nb) != hipSuccess) return;
-    if (split_conv_weights(c.w, nmat, c.Cout, c.K, c.Cin1, ntap, conv_math, p, nullptr) !=
-            DM_OK ||
-        hipDeviceSynchronize() != hipSuccess) {
-      (void)hipFree(p);
-      return;
-    }
-    split_w[key] = p;
-    split_bytes += nb;
-  }
-  c.ws = p;
-  c.ws_np = conv_math;
-  if (conv_math == 2) {
-    c.ws_rowscale = split_conv_rowscale(p, nmat, c.Cout, c.K);
-    c.range_flag = range_flag;
-  }
-  // the Winograd F(2,3) kernel for the 3x3 convs it takes (DM_CONV_WINO=0: conv_k32, its test oracle)
-  c.wino_ws = nullptr;
-  c.wino_rowscale = nullptr;
-  if (conv_math != 2 || !toggles().wino || !conv_wino_shape_ok(c)) return;
-  if (c.Wout == 4 && c.ksplit != wino_small_ks(c)) return;  // (4 x 4: the plan's split decision)
-  const int fold = c.Cin2 && (c.pro_scale || c.gin_part) && !c.pro_nosilu ? 1 : 0;
-  auto iw = wino_w.find(std::make_pair(c.w, fold));
-  void* wp = nullptr;
-  if (iw != wino_w.end()) {
-    wp = iw->second;
-  } else {
-    const size_t nb = wino_weights_bytes(c.Cout, c.Cin1, c.Cin2);
-    if (hipMalloc(&wp, nb) != hipSuccess) {
-      (void)hipGetLastError();
-      return;
-    }
-    if (wino_weights(c.w, c.Cout, c.Cin1, c.Cin2, fold, wp, nullptr) != DM_OK) {
-      (void)hipFree(wp);
-      return;
-    }
-    wino_w[std::make_pair(c.w, fold)] = wp;
-    split_bytes += nb;
-  }
-  c.wino_ws = wp;
-  c.wino_rowscale = wino_rowscale(wp, c.Cout, c.Cin1, c.Cin2);
-  c.wino_fold = fold;
-}
 
 // The folded weights of a single-head attention block (attn_fold, float64 products of the block's own
 // weights) and their fp16x2 images; null if an allocation or launch fails (the block then runs unfolded).
@@ -267,11 +154,6 @@ const UNetModel::FoldW* UNetModel::fold_for(const AttnP& p) {
   }
   split_bytes += nb - 64;  // (the fold results and images; not the allocation's 64 bytes of alignment slack)
   return &(folds[p.wqkv] = f);
-}
-
-// fp16x2 attention GEMMs: operand exponents (exec_pack.h split_gemm_args)
-void UNetModel::split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act) {
-  split_gemm_args(g, conv_math, w_exp, range_flag, ea, weight, weight_n, eb_act);
 }
 
 // Channels of the first conv / last conv input: dim (models/unet.py:72) or
@@ -480,7 +362,8 @@ static int unet_create(const dm_unet_arch* arch, const float* const* params, con
   m->te_b1 = pk.raw(rd.take(TD, "time_embed Linear 1 bias"), TD);
   m->te_w2 = pk.raw(rd.take((int64_t)TD * TD, "time_embed Linear 2 weight"), (int64_t)TD * TD);
   m->te_b2 = pk.raw(rd.take(TD, "time_embed Linear 2 bias"), TD);
-  m->te_freqs = pk.reserve(D / 2);
+  m->freqs = pk.reserve(D / 2);
+  m->n_freqs = D / 2;
   if (a.variant >= 1 && a.num_classes > 0) {  // unet_categorial_adagn.py:104, adm/unet.py:496-497
     m->class_embed = pk.raw(rd.take((int64_t)a.num_classes * TD, "class_embed / label_emb weight"),
                             (int64_t)a.num_classes * TD);
@@ -700,11 +583,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   pl.math = conv_math;
   pl.H = H;
   pl.W = W;
-  if (!range_flag) {
-    DM_CHECK_HIP(hipMalloc(&range_flag, sizeof(int)));
-    DM_CHECK_HIP(hipMemset(range_flag, 0, sizeof(int)));
-    DM_CHECK_HIP(hipHostMalloc(&range_flag_host, sizeof(int)));
-  }
+  if (const int rcf = ensure_range_flag()) return rcf;
   DM_REQUIRE(H % (1 << (n_levels - 1)) == 0 && W % (1 << (n_levels - 1)) == 0,
              "image size must be divisible by 2^(n_stages-1)");
   bool& alloc_failed = pl.alloc_failed;
@@ -846,7 +725,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   add("timestep_embed", 0, 4.0 * B * D, [=](hipStream_t st) {
     // [sin, cos] (modules.py:56) or ADM [cos, sin] (adm/nn.py:118)
     return timestep_embed(P_->t, B, D, self->arch.variant == 2 ? 1 : 0,
-                          self->te_freqs_set ? self->P(self->te_freqs) : nullptr, e0, st);
+                          self->freqs_set ? self->P(self->freqs) : nullptr, e0, st);
   });
   // the time MLP and the temb projections: M = B rows, skinny. linear_rows where gemm_kernel's 64 x 64 tiles would
   // not fill one round of the CUs (the 512-wide time MLP: 9.7 vs 15 / 24 us at B = 256); the 4992-wide temb projection
@@ -1452,96 +1331,49 @@ extern "C" int dm_unet_create(const dm_unet_arch* arch, const float* const* para
 
 extern "C" int dm_unet_forward(dm_unet* h, const float* x, const int64_t* t, const int64_t* y, int B, int H, int W,
                                float* out, void* stream) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
+  dm::UNetModel* m = dm::model_of(h);
+  DM_ABI_MODEL(m);
   if (!x || !t || !out) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   if (B <= 0 || H <= 0 || W <= 0) { dm::set_error("empty batch or image"); return DM_ERR_ARG; }
   if (static_cast<const void*>(out) == static_cast<const void*>(x)) {
     dm::set_error("out must not alias x");
     return DM_ERR_ARG;
   }
-  dm::UNetModel* m = h->m;
   hipStream_t st = (hipStream_t)stream;
   const size_t nx = (size_t)B * m->arch.in_channels * H * W, no = (size_t)B * m->arch.out_channels * H * W;
-  // at most two passes: the caller's arithmetic, then (fp16x2 met an activation beyond the fp16 range) the
-  // same forward in bf16x3; the model's next forward is fp16x2 again
-  if (const int rco = m->plans.pool->order(st)) return rco;
-  // every exit after order() records the completion event, so a later forward on another stream waits for
-  // whatever this one enqueued over the shared slab, even when it failed part way
-  const int rc_body = [&]() -> int {
-    for (int math = m->run_math();;) {
-      dm::UNetModel::Plan* plp = nullptr;
-      const int rc0 = m->get_plan(B, H, W, math, &plp);
-      if (rc0) return rc0;
-      auto& pl = *plp;
-      DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
-      DM_CHECK_HIP(hipMemcpyAsync(pl.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-      // the labels are read only by the class embedding (class_embed_silu); without one the staging is skipped
-      if (m->has_class) {
-        if (y)
-          DM_CHECK_HIP(hipMemcpyAsync(pl.y, y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        else
-          DM_CHECK_HIP(hipMemsetAsync(pl.y, 0xff, (size_t)B * sizeof(int64_t), st));  // -1: no label
-      }
-      const int rc = pl.run(st);
-      if (rc) return rc;
-      DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
-      if (math != 2 || !m->range_check || m->range_deferred) break;
-      DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      DM_CHECK_HIP(hipStreamSynchronize(st));
-      if (!*m->range_flag_host) break;
-      DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-      m->range_fallbacks++;
-      math = 3;
-    }
-    return DM_OK;
-  }();
-  const int rc_mark = m->plans.pool->mark(st);
-  return rc_body ? rc_body : rc_mark;
+  using Plan = dm::UNetModel::Plan;
+  return dm::run_forward(
+      *m, st, [&](int math, Plan** pl) { return m->get_plan(B, H, W, math, pl); },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
+        DM_CHECK_HIP(hipMemcpyAsync(pl.t, t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        // the labels are read only by the class embedding (class_embed_silu); without one the staging is skipped
+        if (m->has_class) {
+          if (y)
+            DM_CHECK_HIP(hipMemcpyAsync(pl.y, y, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+          else
+            DM_CHECK_HIP(hipMemsetAsync(pl.y, 0xff, (size_t)B * sizeof(int64_t), st));  // -1: no label
+        }
+        return DM_OK;
+      },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DM_OK;
+      });
 }
 
 extern "C" int dm_unet_set_range_deferred(dm_unet* h, int deferred) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  h->m->range_deferred = deferred != 0;
-  return DM_OK;
+  return dm::abi_set_range_deferred(dm::model_of(h), deferred);
 }
-
 extern "C" int dm_unet_range_poll(dm_unet* h, void* stream, int* flagged) {
-  if (!h || !h->m || !flagged) { dm::set_error("null model / argument"); return DM_ERR_STATE; }
-  dm::UNetModel* m = h->m;
-  *flagged = 0;
-  if (!m->range_flag) return DM_OK;  // no fp16x2 plan was ever built
-  hipStream_t st = (hipStream_t)stream;
-  DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-  DM_CHECK_HIP(hipStreamSynchronize(st));
-  if (*m->range_flag_host) {
-    DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-    *flagged = 1;
-    if (m->base_math == 2) {  // the caller re-runs what it computed since the last poll: in bf16x3
-      m->fallback = true;
-      m->range_fallbacks++;
-    }
-  }
-  return DM_OK;
+  return dm::abi_range_poll(dm::model_of(h), (hipStream_t)stream, flagged);
 }
-
-extern "C" int dm_unet_range_fallback(dm_unet* h, int on) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  h->m->fallback = on != 0;
-  return DM_OK;
-}
-
+extern "C" int dm_unet_range_fallback(dm_unet* h, int on) { return dm::abi_range_fallback(dm::model_of(h), on); }
 extern "C" int dm_unet_range_stats(const dm_unet* h, int64_t* fallbacks, int* active) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (fallbacks) *fallbacks = h->m->range_fallbacks;
-  if (active) *active = h->m->run_math();
-  return DM_OK;
+  return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
 }
-
 extern "C" int dm_unet_memory(const dm_unet* h, int64_t* weight_bytes, int64_t* workspace_bytes) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (weight_bytes) *weight_bytes = (int64_t)(h->m->arena_floats * sizeof(float) + h->m->split_bytes);
-  if (workspace_bytes) *workspace_bytes = (int64_t)h->m->plans.pool->bytes();
-  return DM_OK;
+  return dm::abi_memory(dm::model_of(h), weight_bytes, workspace_bytes);
 }
 
 extern "C" int dm_unet_share_workspace(dm_unet* a, dm_unet* b) {
@@ -1551,69 +1383,17 @@ extern "C" int dm_unet_share_workspace(dm_unet* a, dm_unet* b) {
 }
 
 extern "C" int dm_unet_plan_stats(const dm_unet* h, int64_t* builds, int* cached) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (builds) *builds = h->m->plans.builds;
-  if (cached) *cached = (int)h->m->plans.plans.size();
-  return DM_OK;
+  return dm::abi_plan_stats(dm::model_of(h), builds, cached);
 }
-
-extern "C" int dm_unet_set_conv_math(dm_unet* h, int kind) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (kind != 0 && kind != DM_SPLIT_BF16X3 && kind != DM_SPLIT_FP16X2) {
-    dm::set_error("conv math must be 0 (fp32), DM_SPLIT_BF16X3 or DM_SPLIT_FP16X2");
-    return DM_ERR_ARG;
-  }
-  h->m->fallback = false;
-  if (kind != h->m->base_math) {
-    h->m->base_math = kind;
-    h->m->plans.clear();
-  }
-  return DM_OK;
-}
-
-extern "C" int dm_unet_get_conv_math(const dm_unet* h, int* kind) {
-  if (!h || !h->m || !kind) { dm::set_error("null model"); return DM_ERR_STATE; }
-  *kind = h->m->base_math;
-  return DM_OK;
-}
-
+extern "C" int dm_unet_set_conv_math(dm_unet* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, true); }
+extern "C" int dm_unet_get_conv_math(const dm_unet* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
 extern "C" int dm_unet_set_time_freqs(dm_unet* h, const float* freqs, int n, void* stream) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (!freqs) {
-    h->m->te_freqs_set = false;
-    h->m->plans.invalidate_graphs();
-    return DM_OK;
-  }
-  if (n != h->m->arch.dim / 2) { dm::set_error("time frequency table must have dim/2 entries"); return DM_ERR_ARG; }
-  DM_CHECK_HIP(hipMemcpyAsync(h->m->P(h->m->te_freqs), freqs, (size_t)n * sizeof(float), hipMemcpyDefault,
-                              (hipStream_t)stream));
-  h->m->te_freqs_set = true;
-  h->m->plans.invalidate_graphs();  // launches read the flag at capture time
-  return DM_OK;
+  return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);
 }
-
-extern "C" int dm_unet_profile(dm_unet* h, int enable) {
-  if (!h || !h->m) { dm::set_error("null model"); return DM_ERR_STATE; }
-  if (!h->m->plans.current()) { dm::set_error("no plan yet: run dm_unet_forward once first"); return DM_ERR_STATE; }
-  h->m->plans.current()->profile_enable(enable);
-  return DM_OK;
-}
-
-extern "C" int dm_unet_profile_count(dm_unet* h, int* n_ops) {
-  if (!h || !h->m || !h->m->plans.current() || !n_ops) { dm::set_error("null model / no plan"); return DM_ERR_STATE; }
-  *n_ops = (int)h->m->plans.current()->ops.size();
-  return DM_OK;
-}
-
+extern "C" int dm_unet_profile(dm_unet* h, int enable) { return dm::abi_profile(dm::model_of(h), enable); }
+extern "C" int dm_unet_profile_count(dm_unet* h, int* n_ops) { return dm::abi_profile_count(dm::model_of(h), n_ops); }
 extern "C" int dm_unet_profile_get(dm_unet* h, int i, char* label, int label_len, double* flops, double* bytes,
                                    double* ms_total, int64_t* launches) {
-  if (!h || !h->m || !h->m->plans.current()) { dm::set_error("null model / no plan"); return DM_ERR_STATE; }
-  return h->m->plans.current()->profile_get(i, label, label_len, flops, bytes, ms_total, launches);
+  return dm::abi_profile_get(dm::model_of(h), i, label, label_len, flops, bytes, ms_total, launches);
 }
-
-extern "C" void dm_unet_destroy(dm_unet* h) {
-  if (!h) return;
-  (void)hipDeviceSynchronize();
-  delete h->m;
-  delete h;
-}
+extern "C" void dm_unet_destroy(dm_unet* h) { dm::abi_destroy(h); }

@@ -1,8 +1,8 @@
 // Building blocks shared by the KL autoencoder's two executors (vae_exec.hip: the decoder, vae_enc_exec.hip: the
 // encoder; reference models/stablediffusion/autoencoder.py): the packed weights of a ResnetBlock (:69-130) and of
-// the single-head AttnBlock (:133-182), the arithmetic state both networks carry (split weights, the fp16 range
-// flag), and the plan builders of the two blocks -- GroupNorm statistics emitted by the producer conv and consumed
-// in the next conv's prologue, the unfused middle attention.
+// the single-head AttnBlock (:133-182), and the plan builders of the two blocks over an ExecNet (exec_core.h: the
+// weight arena, split weights, the fp16 range flag) -- GroupNorm statistics emitted by the producer conv and
+// consumed in the next conv's prologue, the unfused middle attention.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -15,6 +15,7 @@
 #include "dm_kernels.h"
 #include "plan.h"
 #include "exec_pack.h"
+#include "exec_core.h"
 
 namespace dm {
 namespace vaeb {
@@ -102,132 +103,10 @@ struct BlockReader {
   }
 };
 
-// The weight arena and the arithmetic state of one network: as UNetModel (unet_exec.hip)
-struct VaeNet {
-  float* arena = nullptr;
-  size_t arena_floats = 0;
-  // arithmetic and the fp16 range fallback
-  int base_math = conv_math_from_env();
-  int conv_math = base_math;
-  bool range_check = toggles().range_check;
-  int* range_flag = nullptr;
-  int* range_flag_host = nullptr;
-  long range_fallbacks = 0;
-  std::map<std::pair<const float*, int>, void*> split_w;
-  std::map<std::pair<const float*, int>, void*> wino_w;
-  size_t split_bytes = 0;
-  std::map<const float*, int> w_exp;
-
-  VaeNet() = default;
-  VaeNet(const VaeNet&) = delete;
-  VaeNet& operator=(const VaeNet&) = delete;
-  float* P(size_t off) const { return arena + off; }
-  void free_net() {
-    for (auto& kv : split_w) (void)hipFree(kv.second);
-    for (auto& kv : wino_w) (void)hipFree(kv.second);
-    split_w.clear();
-    wino_w.clear();
-    if (range_flag) (void)hipFree(range_flag);
-    if (range_flag_host) (void)hipHostFree(range_flag_host);
-    if (arena) (void)hipFree(arena);
-    range_flag = nullptr;
-    range_flag_host = nullptr;
-    arena = nullptr;
-  }
-  int ensure_range_flag() {
-    if (!range_flag) {
-      DM_CHECK_HIP(hipMalloc(&range_flag, sizeof(int)));
-      DM_CHECK_HIP(hipMemset(range_flag, 0, sizeof(int)));
-      DM_CHECK_HIP(hipHostMalloc(&range_flag_host, sizeof(int)));
-    }
-    return DM_OK;
-  }
-
-  // The split copy (and, for the shapes conv_wino takes, the Winograd weights) of a conv's packed weights, as
-  // UNetModel::split_for; none: the conv stays on the fp32 kernels. A bottom/right-padded stride-2 conv that
-  // conv_split_eligible (conv_patch3 MODE 4's 384-pixel patch) turns down also gets split weights when conv_k32
-  // itself would run it given them (the encoder's first downsamples: the whole-row tile's 390-pixel patch at
-  // Wout = 64, the row-segment tile beyond), and only then: no split copy is made for a conv that stays on im2col.
-  void split_for(ConvArgs& c) {
-    c.ws = nullptr;
-    c.ws_np = 0;
-    c.ws_rowscale = nullptr;
-    c.range_flag = nullptr;
-    c.wino_ws = nullptr;
-    c.wino_rowscale = nullptr;
-    bool s2seg = false;
-    if (conv_math == 2 && c.s2_pad0 && c.stride == 2 && c.taps == 9) {
-      ConvArgs t = c;
-      t.ws = reinterpret_cast<const void*>(16);  // placeholders: the shape checks only
-      t.ws_np = 2;
-      t.ws_rowscale = reinterpret_cast<const float*>(16);
-      const int v = conv_k32_pick(t);
-      s2seg = v == 9 || v == 13;
-    }
-    if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)) || s2seg)) return;
-    if ((c.taps == 1 || c.stride == 2) && conv_math != 2) return;  // the split 1x1 / stride-2 paths are fp16x2 only
-    const int nmat = c.upsample == 2 ? 4 : 1;
-    const int ntap = c.upsample == 2 ? 4 : c.taps;
-    const auto key = std::make_pair(c.w, conv_math);
-    auto it = split_w.find(key);
-    void* p = nullptr;
-    if (it != split_w.end()) {
-      p = it->second;
-    } else {
-      const size_t nb = split_conv_weights_bytes(nmat, c.Cout, c.K, conv_math);
-      if (hipMalloc(&p, nb) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-      }
-      if (split_conv_weights(c.w, nmat, c.Cout, c.K, c.Cin1, ntap, conv_math, p, nullptr) != DM_OK ||
-          hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(p);
-        return;
-      }
-      split_w[key] = p;
-      split_bytes += nb;
-    }
-    c.ws = p;
-    c.ws_np = conv_math;
-    if (conv_math == 2) {
-      c.ws_rowscale = split_conv_rowscale(p, nmat, c.Cout, c.K);
-      c.range_flag = range_flag;
-    }
-    if (conv_math != 2 || !toggles().wino || !conv_wino_shape_ok(c)) return;
-    if (c.Wout == 4) return;  // (4-pixel-wide maps: the Winograd kernel there is a split-K form the UNet plans tune)
-    const int fold = c.Cin2 && (c.pro_scale || c.gin_part) && !c.pro_nosilu ? 1 : 0;
-    auto iw = wino_w.find(std::make_pair(c.w, fold));
-    void* wp = nullptr;
-    if (iw != wino_w.end()) {
-      wp = iw->second;
-    } else {
-      const size_t nb = wino_weights_bytes(c.Cout, c.Cin1, c.Cin2);
-      if (hipMalloc(&wp, nb) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-      }
-      if (wino_weights(c.w, c.Cout, c.Cin1, c.Cin2, fold, wp, nullptr) != DM_OK) {
-        (void)hipFree(wp);
-        return;
-      }
-      wino_w[std::make_pair(c.w, fold)] = wp;
-      split_bytes += nb;
-    }
-    c.wino_ws = wp;
-    c.wino_rowscale = wino_rowscale(wp, c.Cout, c.Cin1, c.Cin2);
-    c.wino_fold = fold;
-  }
-
-  // fp16x2 attention GEMMs: operand exponents (exec_pack.h split_gemm_args)
-  void split_gemm(GemmArgs& g, int ea, const float* weight, size_t weight_n, int eb_act) {
-    split_gemm_args(g, conv_math, w_exp, range_flag, ea, weight, weight_n, eb_act);
-  }
-};
-
 // Plan-build time: the activation buffers of one plan and the builders of the two blocks over them. Lives for one
 // build_plan call; every launch closure copies what it reads (no closure keeps a pointer to the planner).
 struct BlockPlanner {
-  VaeNet* net;
+  ExecNet* net;
   PlanBase& pl;
   int B, G;
   float eps;
@@ -246,7 +125,7 @@ struct BlockPlanner {
   int emit_next = 0;
   int cur_buf = 0;
 
-  BlockPlanner(VaeNet* n, PlanBase& p, int B_, int G_, float eps_) : net(n), pl(p), B(B_), G(G_), eps(eps_) {}
+  BlockPlanner(ExecNet* n, PlanBase& p, int B_, int G_, float eps_) : net(n), pl(p), B(B_), G(G_), eps(eps_) {}
 
   // three rotating activation buffers + hbuf + abuf of max_t floats per image, the statistics and table buffers, and
   // the attention scratch for hw0 tokens of Ca channels

@@ -8,7 +8,8 @@
 // norm_out -> SiLU -> conv_out (2 z_channels) -> quant_conv (1x1) -> mean | logvar -> clamp -> z.
 // No attention outside the middle block, no time embedding.
 //
-// The blocks, their weights and the arithmetic state are vae_blocks.h's, shared with the decoder. The plan (per
+// The blocks and their weights are vae_blocks.h's, shared with the decoder; the arithmetic state, the forward driver
+// and the ABI bodies are exec_core.h's. The plan (per
 // (B, H, W) and arithmetic) ends at conv_out's NCHW output; the posterior kernel runs after it on the caller's
 // buffers, since the noise, the scale and which outputs are wanted change from call to call.
 #include <algorithm>
@@ -87,7 +88,7 @@ struct EncLevelW {
 
 }  // namespace
 
-struct VaeEncoder : vaeb::VaeNet {
+struct VaeEncoder : ExecNet {
   dm_vae_enc_arch arch;
   size_t in_w = 0, in_b = 0;  // conv_in, torch layout [ch][in_channels][3][3]
   std::vector<EncLevelW> levels;
@@ -106,9 +107,7 @@ struct VaeEncoder : vaeb::VaeNet {
   PlanCache<Plan> plans;
   float* out_packed = nullptr;  // conv_out weights as [9][C][CO] (small_out_pack)
   ~VaeEncoder() {
-    plans.clear();
     if (out_packed) (void)hipFree(out_packed);
-    free_net();
   }
   int build_plan(Plan& pl, int B, int H, int W);
   int get_plan(int B, int H, int W, int math, Plan** out) {
@@ -332,12 +331,6 @@ struct dm_vae_encoder {
   dm::VaeEncoder* m;
 };
 
-#define DM_VAE_ENC(h)                             \
-  if (!(h) || !(h)->m) {                          \
-    dm::set_error("null encoder");                \
-    return DM_ERR_STATE;                          \
-  }
-
 extern "C" int dm_vae_encoder_param_count(const dm_vae_enc_arch* arch, int* n_params) {
   const int rc = dm::vae_enc_validate(arch);
   if (rc) return rc;
@@ -358,10 +351,10 @@ extern "C" int dm_vae_encoder_create(const dm_vae_enc_arch* arch, const float* c
 
 extern "C" int dm_vae_encoder_forward(dm_vae_encoder* e, const float* x, int B, int H, int W, const float* noise,
                                       float scale, float* z_out, float* moments_out, void* stream) {
-  DM_VAE_ENC(e);
+  dm::VaeEncoder* m = dm::model_of(e);
+  DM_ABI_MODEL(m);
   if (!x || !z_out) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   if (B <= 0 || H <= 0 || W <= 0) { dm::set_error("empty batch or image"); return DM_ERR_ARG; }
-  dm::VaeEncoder* m = e->m;
   hipStream_t st = (hipStream_t)stream;
   const int f = 1 << (m->arch.n_levels - 1);
   if (H % f != 0 || W % f != 0) {
@@ -381,103 +374,49 @@ extern "C" int dm_vae_encoder_forward(dm_vae_encoder* e, const float* x, int B, 
   }
   const int zc = m->arch.z_channels;
   const size_t nx = (size_t)B * m->arch.in_channels * H * W;
-  if (const int rco = m->plans.pool->order(st)) return rco;
-  const int rc_body = [&]() -> int {
-    // at most two passes: the caller's arithmetic, then (fp16x2 met an activation beyond the fp16 range) bf16x3
-    dm::VaeEncoder::Plan* plp = nullptr;
-    for (int math = m->base_math;;) {
-      const int rc0 = m->get_plan(B, H, W, math, &plp);
-      if (rc0) return rc0;
-      auto& pl = *plp;
-      DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
-      const int rc = pl.run(st);
-      if (rc) return rc;
-      if (math != 2 || !m->range_check) break;
-      DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      DM_CHECK_HIP(hipStreamSynchronize(st));
-      if (!*m->range_flag_host) break;
-      DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-      m->range_fallbacks++;
-      math = 3;
-    }
-    // the posterior, on the caller's buffers
-    const long hw = (long)h0 * w0, n = (long)B * hw;
-    const float* qw = m->arch.quant ? m->P(m->q_w) : nullptr;
-    const float* qb = m->arch.quant ? m->P(m->q_b) : nullptr;
-    hipLaunchKernelGGL(dm::vae_moments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, plp->h, zc, hw, n, qw,
-                       qb, noise, scale, z_out, moments_out);
-    DM_LAUNCH_CHECK();
-    return DM_OK;
-  }();
-  const int rc_mark = m->plans.pool->mark(st);
-  return rc_body ? rc_body : rc_mark;
+  using Plan = dm::VaeEncoder::Plan;
+  return dm::run_forward(
+      *m, st, [&](int math, Plan** pl) { return m->get_plan(B, H, W, math, pl); },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(pl.x, x, nx * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DM_OK;
+      },
+      [&](Plan& pl) {
+        // the posterior, on the caller's buffers (a fallback pass writes them again)
+        const long hw = (long)h0 * w0, n = (long)B * hw;
+        const float* qw = m->arch.quant ? m->P(m->q_w) : nullptr;
+        const float* qb = m->arch.quant ? m->P(m->q_b) : nullptr;
+        hipLaunchKernelGGL(dm::vae_moments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pl.h, zc, hw, n,
+                           qw, qb, noise, scale, z_out, moments_out);
+        DM_LAUNCH_CHECK();
+        return DM_OK;
+      });
 }
 
 extern "C" int dm_vae_encoder_range_stats(const dm_vae_encoder* e, int64_t* fallbacks, int* active) {
-  DM_VAE_ENC(e);
-  if (fallbacks) *fallbacks = e->m->range_fallbacks;
-  if (active) *active = e->m->base_math;
-  return DM_OK;
+  return dm::abi_range_stats(dm::model_of(e), fallbacks, active);
 }
-
 extern "C" int dm_vae_encoder_memory(const dm_vae_encoder* e, int64_t* weight_bytes, int64_t* workspace_bytes) {
-  DM_VAE_ENC(e);
-  if (weight_bytes) *weight_bytes = (int64_t)(e->m->arena_floats * sizeof(float) + e->m->split_bytes);
-  if (workspace_bytes) *workspace_bytes = (int64_t)e->m->plans.pool->bytes();
-  return DM_OK;
+  return dm::abi_memory(dm::model_of(e), weight_bytes, workspace_bytes);
 }
-
 extern "C" int dm_vae_encoder_plan_stats(const dm_vae_encoder* e, int64_t* builds, int* cached) {
-  DM_VAE_ENC(e);
-  if (builds) *builds = e->m->plans.builds;
-  if (cached) *cached = (int)e->m->plans.plans.size();
-  return DM_OK;
+  return dm::abi_plan_stats(dm::model_of(e), builds, cached);
 }
-
 extern "C" int dm_vae_encoder_set_math(dm_vae_encoder* e, int kind) {
-  DM_VAE_ENC(e);
-  if (kind != 0 && kind != DM_SPLIT_BF16X3 && kind != DM_SPLIT_FP16X2) {
-    dm::set_error("encoder math must be 0 (fp32), DM_SPLIT_BF16X3 or DM_SPLIT_FP16X2");
-    return DM_ERR_ARG;
-  }
-  if (kind != e->m->base_math) {
-    e->m->base_math = kind;
-    e->m->plans.clear();
-  }
-  return DM_OK;
+  return dm::abi_set_math(dm::model_of(e), kind, true);
 }
-
 extern "C" int dm_vae_encoder_get_math(const dm_vae_encoder* e, int* kind) {
-  DM_VAE_ENC(e);
-  if (!kind) { dm::set_error("kind is null"); return DM_ERR_ARG; }
-  *kind = e->m->base_math;
-  return DM_OK;
+  if (dm::model_of(e) && !kind) { dm::set_error("kind is null"); return DM_ERR_ARG; }
+  return dm::abi_get_math(dm::model_of(e), kind);
 }
-
 extern "C" int dm_vae_encoder_profile(dm_vae_encoder* e, int enable) {
-  DM_VAE_ENC(e);
-  if (!e->m->plans.current()) { dm::set_error("no plan yet: run dm_vae_encoder_forward once first"); return DM_ERR_STATE; }
-  e->m->plans.current()->profile_enable(enable);
-  return DM_OK;
+  return dm::abi_profile(dm::model_of(e), enable);
 }
-
 extern "C" int dm_vae_encoder_profile_count(dm_vae_encoder* e, int* n_ops) {
-  DM_VAE_ENC(e);
-  if (!e->m->plans.current() || !n_ops) { dm::set_error("no plan"); return DM_ERR_STATE; }
-  *n_ops = (int)e->m->plans.current()->ops.size();
-  return DM_OK;
+  return dm::abi_profile_count(dm::model_of(e), n_ops);
 }
-
 extern "C" int dm_vae_encoder_profile_get(dm_vae_encoder* e, int i, char* label, int label_len, double* flops,
                                           double* bytes, double* ms_total, int64_t* launches) {
-  DM_VAE_ENC(e);
-  if (!e->m->plans.current()) { dm::set_error("no plan"); return DM_ERR_STATE; }
-  return e->m->plans.current()->profile_get(i, label, label_len, flops, bytes, ms_total, launches);
+  return dm::abi_profile_get(dm::model_of(e), i, label, label_len, flops, bytes, ms_total, launches);
 }
-
-extern "C" void dm_vae_encoder_destroy(dm_vae_encoder* e) {
-  if (!e) return;
-  (void)hipDeviceSynchronize();
-  delete e->m;
-  delete e;
-}
+extern "C" void dm_vae_encoder_destroy(dm_vae_encoder* e) { dm::abi_destroy(e); }

@@ -11,8 +11,8 @@
 // ResnetBlock's nin_shortcut is the second K segment of its conv2 (bias b2 + bs); q, k, v -> one [3C][C] weight;
 // upsample convs also in the sub-pixel form. The plan (per (B, H, W) and arithmetic) runs over five activation
 // buffers sized to the largest tensor of the network, reused by every level (a level's tensors die at its upsample).
-// The ResnetBlock / attention weights and plan builders and the arithmetic state are vae_blocks.h's, shared with the
-// encoder (vae_enc_exec.hip).
+// The ResnetBlock / attention weights and plan builders are vae_blocks.h's, shared with the encoder
+// (vae_enc_exec.hip); the arithmetic state, the forward driver and the ABI bodies are exec_core.h's.
 #include <algorithm>
 #include <cmath>
 #include <functional>
@@ -72,7 +72,7 @@ struct LevelW {
 
 }  // namespace
 
-struct VaeDecoder : vaeb::VaeNet {
+struct VaeDecoder : ExecNet {
   dm_vae_arch arch;
   size_t pq_w = 0, pq_b = 0;  // post_quant_conv [zc][zc], [zc]
   size_t in_w = 0, in_b = 0;  // conv_in, torch layout [C][zc][3][3]
@@ -91,11 +91,9 @@ struct VaeDecoder : vaeb::VaeNet {
   };
   PlanCache<Plan> plans;
   float* out_packed = nullptr;  // conv_out weights as [9][C][CO] (small_out_pack)
-  // (the weight arena, the arithmetic and the fp16 range fallback: vaeb::VaeNet)
+  // (the weight arena, the arithmetic and the fp16 range fallback: ExecNet)
   ~VaeDecoder() {
-    plans.clear();
     if (out_packed) (void)hipFree(out_packed);
-    free_net();
   }
   int build_plan(Plan& pl, int B, int H, int W);
   int get_plan(int B, int H, int W, int math, Plan** out) {
@@ -348,12 +346,6 @@ struct dm_vae_decoder {
   dm::VaeDecoder* m;
 };
 
-#define DM_VAE_MODEL(h)                           \
-  if (!(h) || !(h)->m) {                          \
-    dm::set_error("null decoder");                \
-    return DM_ERR_STATE;                          \
-  }
-
 extern "C" int dm_vae_decoder_param_count(const dm_vae_arch* arch, int* n_params) {
   const int rc = dm::vae_validate(arch);
   if (rc) return rc;
@@ -374,14 +366,14 @@ extern "C" int dm_vae_decoder_create(const dm_vae_arch* arch, const float* const
 
 extern "C" int dm_vae_decoder_forward(dm_vae_decoder* h, const float* z, int B, int H, int W, float scale, float* out,
                                       void* stream) {
-  DM_VAE_MODEL(h);
+  dm::VaeDecoder* m = dm::model_of(h);
+  DM_ABI_MODEL(m);
   if (!z || !out) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   if (B <= 0 || H <= 0 || W <= 0) { dm::set_error("empty batch or latent"); return DM_ERR_ARG; }
   if (static_cast<const void*>(out) == static_cast<const void*>(z)) {
     dm::set_error("out must not alias z");
     return DM_ERR_ARG;
   }
-  dm::VaeDecoder* m = h->m;
   hipStream_t st = (hipStream_t)stream;
   const int up = 1 << (m->arch.n_levels - 1);
   // the middle attention's score rows (L = H W floats) are read as 16-byte vectors by the GEMMs
@@ -395,101 +387,47 @@ extern "C" int dm_vae_decoder_forward(dm_vae_decoder* h, const float* z, int B, 
   }
   const size_t nz = (size_t)B * m->arch.z_channels * H * W;
   const size_t no = (size_t)B * m->arch.out_channels * H * up * W * up;
-  if (const int rco = m->plans.pool->order(st)) return rco;
-  const int rc_body = [&]() -> int {
-    // at most two passes: the caller's arithmetic, then (fp16x2 met an activation beyond the fp16 range) bf16x3
-    for (int math = m->base_math;;) {
-      dm::VaeDecoder::Plan* plp = nullptr;
-      const int rc0 = m->get_plan(B, H, W, math, &plp);
-      if (rc0) return rc0;
-      auto& pl = *plp;
-      if (pl.scale != scale) {  // the latent-entry launch reads the scale at capture time
-        pl.scale = scale;
-        pl.invalidate_graph();
-      }
-      DM_CHECK_HIP(hipMemcpyAsync(pl.z, z, nz * sizeof(float), hipMemcpyDeviceToDevice, st));
-      const int rc = pl.run(st);
-      if (rc) return rc;
-      DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
-      if (math != 2 || !m->range_check) break;
-      DM_CHECK_HIP(hipMemcpyAsync(m->range_flag_host, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-      DM_CHECK_HIP(hipStreamSynchronize(st));
-      if (!*m->range_flag_host) break;
-      DM_CHECK_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-      m->range_fallbacks++;
-      math = 3;
-    }
-    return DM_OK;
-  }();
-  const int rc_mark = m->plans.pool->mark(st);
-  return rc_body ? rc_body : rc_mark;
+  using Plan = dm::VaeDecoder::Plan;
+  return dm::run_forward(
+      *m, st, [&](int math, Plan** pl) { return m->get_plan(B, H, W, math, pl); },
+      [&](Plan& pl) {
+        if (pl.scale != scale) {  // the latent-entry launch reads the scale at capture time
+          pl.scale = scale;
+          pl.invalidate_graph();
+        }
+        DM_CHECK_HIP(hipMemcpyAsync(pl.z, z, nz * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DM_OK;
+      },
+      [&](Plan& pl) {
+        DM_CHECK_HIP(hipMemcpyAsync(out, pl.out, no * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DM_OK;
+      });
 }
 
 extern "C" int dm_vae_decoder_range_stats(const dm_vae_decoder* h, int64_t* fallbacks, int* active) {
-  DM_VAE_MODEL(h);
-  if (fallbacks) *fallbacks = h->m->range_fallbacks;
-  if (active) *active = h->m->base_math;
-  return DM_OK;
+  return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
 }
-
 extern "C" int dm_vae_decoder_memory(const dm_vae_decoder* h, int64_t* weight_bytes, int64_t* workspace_bytes) {
-  DM_VAE_MODEL(h);
-  if (weight_bytes) *weight_bytes = (int64_t)(h->m->arena_floats * sizeof(float) + h->m->split_bytes);
-  if (workspace_bytes) *workspace_bytes = (int64_t)h->m->plans.pool->bytes();
-  return DM_OK;
+  return dm::abi_memory(dm::model_of(h), weight_bytes, workspace_bytes);
 }
-
 extern "C" int dm_vae_decoder_plan_stats(const dm_vae_decoder* h, int64_t* builds, int* cached) {
-  DM_VAE_MODEL(h);
-  if (builds) *builds = h->m->plans.builds;
-  if (cached) *cached = (int)h->m->plans.plans.size();
-  return DM_OK;
+  return dm::abi_plan_stats(dm::model_of(h), builds, cached);
 }
-
 extern "C" int dm_vae_decoder_set_math(dm_vae_decoder* h, int kind) {
-  DM_VAE_MODEL(h);
-  if (kind != 0 && kind != DM_SPLIT_BF16X3 && kind != DM_SPLIT_FP16X2) {
-    dm::set_error("decoder math must be 0 (fp32), DM_SPLIT_BF16X3 or DM_SPLIT_FP16X2");
-    return DM_ERR_ARG;
-  }
-  if (kind != h->m->base_math) {
-    h->m->base_math = kind;
-    h->m->plans.clear();
-  }
-  return DM_OK;
+  return dm::abi_set_math(dm::model_of(h), kind, true);
 }
-
 extern "C" int dm_vae_decoder_get_math(const dm_vae_decoder* h, int* kind) {
-  DM_VAE_MODEL(h);
-  if (!kind) { dm::set_error("kind is null"); return DM_ERR_ARG; }
-  *kind = h->m->base_math;
-  return DM_OK;
+  if (dm::model_of(h) && !kind) { dm::set_error("kind is null"); return DM_ERR_ARG; }
+  return dm::abi_get_math(dm::model_of(h), kind);
 }
-
 extern "C" int dm_vae_decoder_profile(dm_vae_decoder* h, int enable) {
-  DM_VAE_MODEL(h);
-  if (!h->m->plans.current()) { dm::set_error("no plan yet: run dm_vae_decoder_forward once first"); return DM_ERR_STATE; }
-  h->m->plans.current()->profile_enable(enable);
-  return DM_OK;
+  return dm::abi_profile(dm::model_of(h), enable);
 }
-
 extern "C" int dm_vae_decoder_profile_count(dm_vae_decoder* h, int* n_ops) {
-  DM_VAE_MODEL(h);
-  if (!h->m->plans.current() || !n_ops) { dm::set_error("no plan"); return DM_ERR_STATE; }
-  *n_ops = (int)h->m->plans.current()->ops.size();
-  return DM_OK;
+  return dm::abi_profile_count(dm::model_of(h), n_ops);
 }
-
 extern "C" int dm_vae_decoder_profile_get(dm_vae_decoder* h, int i, char* label, int label_len, double* flops,
                                           double* bytes, double* ms_total, int64_t* launches) {
-  DM_VAE_MODEL(h);
-  if (!h->m->plans.current()) { dm::set_error("no plan"); return DM_ERR_STATE; }
-  return h->m->plans.current()->profile_get(i, label, label_len, flops, bytes, ms_total, launches);
+  return dm::abi_profile_get(dm::model_of(h), i, label, label_len, flops, bytes, ms_total, launches);
 }
-
-extern "C" void dm_vae_decoder_destroy(dm_vae_decoder* h) {
-  if (!h) return;
-  (void)hipDeviceSynchronize();
-  delete h->m;
-  delete h;
-}
+extern "C" void dm_vae_decoder_destroy(dm_vae_decoder* h) { dm::abi_destroy(h); }
