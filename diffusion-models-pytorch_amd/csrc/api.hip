@@ -350,11 +350,13 @@ extern "C" int dm_pack_conv_weight_subpixel(const float* w, int Cout, int Cin, f
 }
 
 // dm_gemm; with gn_part (dm_debug_gemm_gn) also the GroupNorm(gn_G) statistics of the output rows, images of gn_hw rows
-static int gemm_from_desc(const dm_gemm_desc* d, double2* gn_part, int gn_G, int gn_hw, void* stream) {
+static int gemm_from_desc(const dm_gemm_desc* d, double2* gn_part, int gn_G, int gn_hw, void* stream,
+                          int64_t pick_M = 0, int64_t pick_Z = 0, bool log = false) {
   dm::refresh_toggles();
   if (!d || !d->A || !d->B || !d->C) { dm::set_error("null tensor"); return DM_ERR_ARG; }
   dm::GemmArgs g{};
   g.M = d->M; g.N = d->N; g.K = d->K; g.Z1 = d->Z1; g.Z2 = d->Z2;
+  g.pick_M = (long)pick_M; g.pick_Z = (long)pick_Z;
   g.A = d->A; g.a_s1 = d->a_s1; g.a_s2 = d->a_s2; g.lda = d->lda;
   g.Bm = d->B; g.b_s1 = d->b_s1; g.b_s2 = d->b_s2; g.ldb = d->ldb; g.b_kn = d->b_kn;
   g.C = d->C; g.c_s1 = d->c_s1; g.c_s2 = d->c_s2; g.ldc = d->ldc;
@@ -362,7 +364,9 @@ static int gemm_from_desc(const dm_gemm_desc* d, double2* gn_part, int gn_G, int
   g.b_scale = d->b_scale;
   g.split = d->split; g.split_ea = d->split_ea; g.split_eb = d->split_eb; g.range_flag = d->range_flag;
   g.gn_part = gn_part; g.gn_G = gn_G; g.gn_hw = gn_hw;
-  return dm::gemm_batched(g, (hipStream_t)stream);
+  const int rc = dm::gemm_batched(g, (hipStream_t)stream);
+  if (log && rc == DM_OK) dm::note_launch(dm::gemm_label(g).c_str());
+  return rc;
 }
 
 extern "C" int dm_gemm(const dm_gemm_desc* d, void* stream) { return gemm_from_desc(d, nullptr, 0, 0, stream); }
@@ -372,6 +376,16 @@ extern "C" int dm_gemm(const dm_gemm_desc* d, void* stream) { return gemm_from_d
 extern "C" int dm_debug_gemm_gn(const dm_gemm_desc* d, int G, int hw, void* part, void* stream) {
   if (!part || G <= 0 || hw <= 0) { dm::set_error("dm_debug_gemm_gn: arguments"); return DM_ERR_ARG; }
   const int rc = gemm_from_desc(d, (double2*)part, G, hw, stream);
+  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DM_OK) { dm::set_error("sync"); return DM_ERR_HIP; }
+  return rc;
+}
+
+// Operator tests of the unfused attention chain (tests/test_gpu_unfused_attention_ops.py): dm_gemm with the tile
+// heuristic's nominal M and Z1 * Z2 (GemmArgs::pick_M / pick_Z, 0: the actual ones) as the plans pass them, so the
+// 128 x 128 batched instances run on a two-image buffer. Synchronous; with the launch log on, gemm_label is logged.
+extern "C" int dm_debug_gemm_pick(const dm_gemm_desc* d, int64_t pick_M, int64_t pick_Z, void* stream) {
+  if (pick_M < 0 || pick_Z < 0) { dm::set_error("dm_debug_gemm_pick: arguments"); return DM_ERR_ARG; }
+  const int rc = gemm_from_desc(d, nullptr, 0, 0, stream, pick_M, pick_Z, true);
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DM_OK) { dm::set_error("sync"); return DM_ERR_HIP; }
   return rc;
 }

@@ -546,6 +546,9 @@ typedef struct dm_gemm_desc {
   int* range_flag;
 } dm_gemm_desc;
 int dm_gemm(const dm_gemm_desc* d, void* stream);
+/* Test hook: dm_gemm with the tile heuristic told a nominal M and batch count (0: the actual ones), as the model
+ * plans do for batch-invariant kernel choice; synchronous. Not for production callers. */
+int dm_debug_gemm_pick(const dm_gemm_desc* d, int64_t pick_M, int64_t pick_Z, void* stream);
 
 int dm_softmax_rows(float* x, int64_t rows, int L, int ld, void* stream);
 /* kind 0: models/modules.py SinusoidalPosEmb ([sin, cos]); kind 1: ADM timestep_embedding ([cos, sin]) */
