@@ -21,6 +21,7 @@ bool env_is(const char* name, char c) {
   return e && e[0] == c;
 }
 bool g_launch_log_on = false;
+bool g_launch_log_convs = false;  // dm_debug_launch_log(2): every dm_conv2d_nhwc* entry logs its conv_label too
 std::string g_launch_log;
 }  // namespace
 const Toggles& toggles() { return t_scope ? *t_scope : t_toggles; }
@@ -64,9 +65,13 @@ void note_launch(const char* name) {
 }
 }  // namespace dm
 
-/* Test hook: enable (1, clearing it) / disable (0) the launch log; read copies it NUL-terminated into buf. */
+/* Test hook: enable (1, clearing it) / disable (0) the launch log; read copies it NUL-terminated into buf.
+   enable = 2: as 1, and every conv entry (dm_conv2d_nhwc, dm_conv2d_nhwc_s2pad0) logs conv_label of its descriptor
+   after the launchers' own lines, as dm_debug_conv2d_gn does -- so a test that forces a tile sees the kernel the
+   dispatcher took for it (a forced tile that does not fit falls back without an error). */
 extern "C" int dm_debug_launch_log(int enable) {
   dm::g_launch_log_on = enable != 0;
+  dm::g_launch_log_convs = enable == 2;
   if (enable) dm::g_launch_log.clear();
   return DM_OK;
 }
@@ -283,10 +288,10 @@ static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part
     }
   }
   const int rc = dm::conv2d_igemm(a, (hipStream_t)stream);
-  // dm_debug_conv2d_gn / dm_debug_conv2d_gin only (null on every other entry): conv_label(a) goes to the launch log after the
+  // dm_debug_conv2d_gn / dm_debug_conv2d_gin (null on every other entry) and dm_debug_launch_log(2): conv_label(a) goes to the launch log after the
   // launchers' own lines. It is the dispatcher's choice restated from the same ConvArgs (the label function the
   // profiles use, which mirrors conv2d_igemm's dispatch), not a record made by the launcher.
-  if ((gn_part || gin) && rc == DM_OK) dm::note_launch(dm::conv_label(a).c_str());
+  if ((gn_part || gin || dm::g_launch_log_convs) && rc == DM_OK) dm::note_launch(dm::conv_label(a).c_str());
   return rc;
 }
 

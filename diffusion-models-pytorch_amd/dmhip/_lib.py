@@ -661,10 +661,12 @@ def unet_profile_read(handle, abi: str = 'dm_unet'):
     return out
 
 
-def launch_log(enable: bool) -> None:
+def launch_log(enable: bool, convs: bool = False) -> None:
     """Start (clearing it) or stop the library's launch log: the kernel instantiations its conv launchers issue
-    (dm_debug_launch_log; a hipGraph plan launches at capture, i.e. on the forward that builds the plan)."""
-    check(load().dm_debug_launch_log(1 if enable else 0), 'dm_debug_launch_log')
+    (dm_debug_launch_log; a hipGraph plan launches at capture, i.e. on the forward that builds the plan).
+    convs = True: conv2d_nhwc / conv2d_nhwc_s2pad0 also log the kernel instantiation the dispatcher took for their
+    descriptor (conv_label), after the launchers' own lines."""
+    check(load().dm_debug_launch_log((2 if convs else 1) if enable else 0), 'dm_debug_launch_log')
 
 
 def launch_log_read() -> list:
