@@ -132,8 +132,13 @@ struct DiTModel : ExecNet {
     if (sk_cnt) (void)hipFree(sk_cnt);
   }
   int build_plan(Plan& pl, int B);
+  // DM_MATH_FP16 (m == 1): a plan of the fp16x2 arithmetic (conv_math 2: the attention products, the adaLN GEMM and
+  // whatever linear_h16_ok refuses are built exactly as in that mode) whose covered static-weight token GEMMs run
+  // linear_h16.hip on piece 0 of the same fragment images -- no second weight copy
+  bool h16_plan = false;
   int get_plan(int B, int m, Plan** out) {
-    conv_math = m;
+    h16_plan = m == DM_MATH_FP16;
+    conv_math = h16_plan ? 2 : m;
     return plans.get([&](const Plan& p) { return p.B == B && p.math == m; }, [&](Plan& p) { return build_plan(p, B); },
                      out);
   }
@@ -280,7 +285,8 @@ int DiTModel::build_plan(Plan& pl, int B) {
   ToggleScope scope(pl.toggles);
   pl.graph_enabled = toggles().graph;
   pl.B = B;
-  pl.math = conv_math;
+  const bool h16 = h16_plan;
+  pl.math = h16 ? DM_MATH_FP16 : conv_math;
   const dm_dit_arch& a = arch;
   const int p = a.patch_size, C = a.in_channels, S = a.input_size, Hm = a.mlp_hidden;
   const int heads = a.num_heads, Dh = D / heads;
@@ -351,7 +357,31 @@ int DiTModel::build_plan(Plan& pl, int B) {
     const float* sx = stats_src;
     pl.add("row_stats", 0, 4.0 * M * D, [=](hipStream_t st) { return row_stats(sx, M, D, ln_eps, stats, st); });
   };
+  // DM_MATH_FP16: the A image (one fp16 plane) of a covered GEMM, always by its own pass (at every M: the kernel
+  // takes A in no other form), LayerNorm statistics from row_stats first; the buffer is the split path's
+  auto add_h16_gemm = [&](GemmArgs g) {
+    if (g.as) {  // the image came from a producer (fc1's c_split)
+      add_gemm(g);
+      return;
+    }
+    const size_t need = (size_t)g.M * g.K * 2;
+    if (need > as_bytes) {
+      as_buf = reinterpret_cast<_Float16*>(pl.alloc(need));
+      as_bytes = need;
+    }
+    flush_stats();
+    _Float16* buf = as_buf;
+    pl.add("linear_h16_image", 0, 6.0 * g.M * g.K, [=](hipStream_t st) { return linear_h16_image(g, buf, st); });
+    g.as = buf;
+    g.pro_scale = g.pro_shift = nullptr;
+    g.ln_stats = nullptr;
+    add_gemm(g);
+  };
   auto add_token_gemm = [&](GemmArgs g) {
+    if (g.h16) {
+      add_h16_gemm(g);
+      return;
+    }
     // nominal-batch decision (pick_M = T * kPickBatch): the same kernels at every B, so results are
     // batch-invariant (each image's row block of B * T tokens runs the same code)
     if (g.ws && presplit_on && g.pick_M >= 4096) {
@@ -386,7 +416,8 @@ int DiTModel::build_plan(Plan& pl, int B) {
   };
   // fp16x2 operand exponents (ExecNet::split_gemm): weights by max |w|, activations fixed (2^6 for
   // LayerNorm-modulated tokens, q, k, v, attention and MLP outputs; 2^14 for softmax rows)
-  auto split = [&](GemmArgs& g, int ea, size_t w, size_t wn, int eb_act) {
+  // cover: a GEMM DM_MATH_FP16 covers (every static-weight token GEMM but the adaLN one)
+  auto split = [&](GemmArgs& g, int ea, size_t w, size_t wn, int eb_act, bool cover = true) {
     split_gemm(g, ea, wn ? P(w) : nullptr, wn, eb_act);
     if (conv_math != 2) return;
     // static weight [N][K]: pre-split once for linear_k32 (the gemm.hip path stays the fallback)
@@ -414,6 +445,19 @@ int DiTModel::build_plan(Plan& pl, int B) {
         g.sk_ws = sk_ws;
         g.sk_cnt = sk_cnt;
         g.sk_cap = sk_cap;
+      }
+      if (h16 && cover) {  // the launch form: the image in `as`, the prologue done by the image pass
+        GemmArgs ph = g;
+        ph.h16 = 1;
+        ph.ln_stats = nullptr;
+        ph.pro_scale = ph.pro_shift = nullptr;
+        ph.as = reinterpret_cast<const _Float16*>(uintptr_t(256));  // only its alignment is checked
+        if (linear_h16_ok(ph)) {
+          g.h16 = 1;
+          g.sk_ws = nullptr;  // (no split-K tail in this arithmetic)
+          g.sk_cnt = nullptr;
+          return;
+        }
       }
       // with the pre-split A image (add_token_gemm) the GEMM takes no prologue: check that form
       GemmArgs probe = g;
@@ -458,7 +502,9 @@ int DiTModel::build_plan(Plan& pl, int B) {
   // 128 columns streaming its K x 128 slice (the fp32 gemm_kernel took 558 us, 1.6 TB/s)
   {
     GemmArgs g = linear(se, D, B, ada_w, ada_b, ada_total, D, mods, ada_total);
-    split(g, 6, ada_w, (size_t)ada_total * D, 6);
+    // (DM_MATH_FP16 leaves it on linear_k32: M = B rows against the whole weight stream is bandwidth bound, and a
+    // 128-row tile of one product per MAC has nothing to win on B rows)
+    split(g, 6, ada_w, (size_t)ada_total * D, 6, false);
     add_gemm(g);
   }
 
@@ -503,7 +549,7 @@ int DiTModel::build_plan(Plan& pl, int B) {
     split(gpj, 6, bp.proj_w, (size_t)D * D, 0);
     GemmArgs gpj_as = gpj;
     gpj_as.as = reinterpret_cast<const _Float16*>(Ob);
-    const bool o_presplit = flash && presplit_on && D % 32 == 0 && gpj.ws && gpj.split_ea == 6 && linear_k32_ok(gpj_as);
+    const bool o_presplit = flash && !gpj.h16 && presplit_on && D % 32 == 0 && gpj.ws && gpj.split_ea == 6 && linear_k32_ok(gpj_as);
     if (flash) {
       AttnArgs at{};
       at.pq = planes; at.pk = planes + plane_n; at.pv = planes + 2 * plane_n;
@@ -575,7 +621,16 @@ int DiTModel::build_plan(Plan& pl, int B) {
       g1s.c_split = reinterpret_cast<_Float16*>(hb);
       g1s.c_split_ea = g2.split_ea;
       g2s.as = reinterpret_cast<const _Float16*>(hb);
-      if (presplit_on && g.ws && g2.ws && linear_k32_ok(g1s) && linear_k32_ok(g2s)) {
+      GemmArgs h1 = g1s, h2 = g2s;   // DM_MATH_FP16: the launch forms (fc1's prologue goes to its image pass)
+      h1.ln_stats = nullptr;
+      h1.as = h2.as;
+      if (g.h16 && g2.h16 && linear_h16_ok(h1) && linear_h16_ok(h2)) {
+        add_token_gemm(g1s);   // GELU(h) * 2^ea rounded once, as fc2's image (one fp16 plane over hb)
+        add_token_gemm(g2s);
+      } else if (g.h16 || g2.h16) {
+        add_token_gemm(g);
+        add_token_gemm(g2);
+      } else if (presplit_on && g.ws && g2.ws && linear_k32_ok(g1s) && linear_k32_ok(g2s)) {
         add_token_gemm(g1s);
         add_gemm(g2s);
       } else {
@@ -592,6 +647,26 @@ int DiTModel::build_plan(Plan& pl, int B) {
     {
       GemmArgs g = linear(cur, 2 * D, M, bp.skip_w, bp.skip_b, D, 2 * D, out, D);
       split(g, 6, bp.skip_w, (size_t)D * 2 * D, 0);
+      if (g.h16 && D % 32 == 0) {   // DM_MATH_FP16: the image pass does the concat
+        const size_t need = (size_t)M * 2 * D * 2;
+        if (need > as_bytes) {
+          as_buf = reinterpret_cast<_Float16*>(pl.alloc(need));
+          as_bytes = need;
+        }
+        g.as = as_buf;
+        if (as_buf && linear_h16_ok(g)) {
+          _Float16* buf = as_buf;
+          int* rf = g.range_flag;
+          const int D_ = D;
+          pl.add("linear_h16_image_cat", 0, 12.0 * M * D, [=](hipStream_t st) {
+            return linear_h16_image_cat(cur, skip, M, D_, 6, buf, rf, st);
+          });
+          add_gemm(g);
+          return;
+        }
+        g.as = nullptr;
+      }
+      g.h16 = 0;   // (refused: as in fp16x2)
       if (g.ws && presplit_on && g.pick_M >= 4096 && D % 32 == 0) {
         const size_t need = (size_t)M * 2 * D * 4;
         if (need > as_bytes) {
@@ -734,7 +809,7 @@ extern "C" int dm_dit_range_fallback(dm_dit* h, int on) { return dm::abi_range_f
 extern "C" int dm_dit_range_stats(const dm_dit* h, int64_t* fallbacks, int* active) {
   return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
 }
-extern "C" int dm_dit_set_math(dm_dit* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false); }
+extern "C" int dm_dit_set_math(dm_dit* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false, true); }
 extern "C" int dm_dit_get_math(const dm_dit* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
 extern "C" int dm_dit_set_time_freqs(dm_dit* h, const float* freqs, int n, void* stream) {
   return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);
@@ -793,7 +868,7 @@ extern "C" int dm_mdt_range_fallback(dm_mdt* h, int on) { return dm::abi_range_f
 extern "C" int dm_mdt_range_stats(const dm_mdt* h, int64_t* fallbacks, int* active) {
   return dm::abi_range_stats(dm::model_of(h), fallbacks, active);
 }
-extern "C" int dm_mdt_set_math(dm_mdt* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false); }
+extern "C" int dm_mdt_set_math(dm_mdt* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, false, true); }
 extern "C" int dm_mdt_get_math(const dm_mdt* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
 extern "C" int dm_mdt_set_time_freqs(dm_mdt* h, const float* freqs, int n, void* stream) {
   return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);

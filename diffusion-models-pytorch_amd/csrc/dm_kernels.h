@@ -237,6 +237,10 @@ struct GemmArgs {
   unsigned* sk_cnt;
   int sk_cap;
   int sk_S, sk_tdp;
+  // 1: the half-precision arithmetic DM_MATH_FP16 (linear_h16.hip): one fp16 product per MAC on piece 0 of the
+  // fragment image in ws; `as` is then the single fp16 plane [M][K] of linear_h16_image, c_split a single plane
+  // [M][N] too. (Not `split = 1`: gemm.hip reads split as "0 fp32, 2 fp16x2" and rejects anything else.)
+  int h16;
 };
 
 struct StepArgs {
@@ -351,6 +355,16 @@ int linear_k32(const GemmArgs& g, hipStream_t st);
 int linear_k32_slots();
 // the pre-split A image of g (prologue, alpha, 2^split_ea, fp16x2 split; |value| > 65504 sets range_flag)
 int linear_presplit_a(const GemmArgs& g, _Float16* out, hipStream_t st);
+// DM_MATH_FP16 (linear_h16.hip): static-weight GEMM with one fp16 product per MAC, fp32 accumulation. The launch
+// form linear_h16_ok accepts has GemmArgs::h16 = 1, the fp16 A image in `as` (linear_h16_image: prologue, alpha,
+// 2^split_ea, one rounding to fp16, plane [M][K]; |value| > 65504 sets range_flag -- bit for bit piece 0 of
+// linear_presplit_a's image; linear_h16_image_cat: of [x | skip]) and the fp16x2 fragment image in `ws`, of which it
+// reads piece 0. A descriptor it refuses launches nothing.
+bool linear_h16_ok(const GemmArgs& g);
+int linear_h16(const GemmArgs& g, hipStream_t st);
+int linear_h16_image(const GemmArgs& g, _Float16* out, hipStream_t st);
+int linear_h16_image_cat(const float* x, const float* skip, long M, int D, int ea, _Float16* out, int* range_flag,
+                         hipStream_t st);
 int conv_splitk_reduce(const ConvArgs& a, hipStream_t st);
 // fp32 packed conv weights [nmat][rows][K] -> split slices for conv_patch3_kernel (np 3: bf16x3,
 // np 2: fp16x2 + row scales); split_conv_rowscale gives ConvArgs::ws_rowscale of an fp16x2 copy

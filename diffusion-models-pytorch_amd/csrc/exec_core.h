@@ -30,6 +30,9 @@ inline int wino_small_ks(const ConvArgs& c) {
 // read the flag nor sync; the caller polls it once per sampling loop (abi_range_poll), and its re-run of a flagged
 // loop runs in fallback_math while `fallback` is set (abi_range_fallback clears it). DM_RANGE_CHECK=0 skips the
 // check and its sync. conv_math is the arithmetic of the plan being built (set by the model's get_plan).
+// DM_MATH_FP16 (1, the token models only: dit_exec.hip) is range-checked in the same way: its operands are fp16 too.
+inline bool math_range_checked(int kind) { return kind == DM_SPLIT_FP16X2 || kind == DM_MATH_FP16; }
+
 struct ExecNet {
   float* arena = nullptr;
   size_t arena_floats = 0;
@@ -63,7 +66,7 @@ struct ExecNet {
     if (arena) (void)hipFree(arena);
   }
   float* P(size_t off) const { return arena + off; }
-  int run_math() const { return base_math == 2 && fallback ? fallback_math : base_math; }
+  int run_math() const { return math_range_checked(base_math) && fallback ? fallback_math : base_math; }
 
   int ensure_range_flag() {
     if (!range_flag) {
@@ -197,7 +200,7 @@ int run_forward(M& m, hipStream_t st, GetPlan get_plan, StageIn stage_in, StageO
       if (const int rc = stage_in(*pl)) return rc;
       if (const int rc = pl->run(st)) return rc;
       if (const int rc = stage_out(*pl)) return rc;
-      if (math != 2 || !m.range_check || m.range_deferred) return DM_OK;
+      if (!math_range_checked(math) || !m.range_check || m.range_deferred) return DM_OK;
       bool raised = false;
       if (const int rc = m.take_range_flag(st, &raised)) return rc;
       if (!raised) return DM_OK;
@@ -236,7 +239,7 @@ inline int abi_range_poll(ExecNet* m, hipStream_t st, int* flagged) {
   if (const int rc = m->take_range_flag(st, &raised)) return rc;
   if (raised) {
     *flagged = 1;
-    if (m->base_math == 2) {  // the caller re-runs what it computed since the last poll: in fallback_math
+    if (math_range_checked(m->base_math)) {  // the caller re-runs what it computed since the last poll: in fallback_math
       m->fallback = true;
       m->range_fallbacks++;
     }
@@ -263,12 +266,15 @@ inline int abi_get_math(const ExecNet* m, int* kind) {
   return DM_OK;
 }
 
-// bf16x3_ok: the conv nets take 0, fp16x2 and bf16x3; the token models 0 and fp16x2 only
+// bf16x3_ok: the conv nets take 0, fp16x2 and bf16x3; fp16_ok: the token models take 0, fp16x2 and DM_MATH_FP16
 template <class M>
-int abi_set_math(M* m, int kind, bool bf16x3_ok) {
+int abi_set_math(M* m, int kind, bool bf16x3_ok, bool fp16_ok = false) {
   DM_ABI_MODEL(m);
-  if (kind != 0 && kind != DM_SPLIT_FP16X2 && !(bf16x3_ok && kind == DM_SPLIT_BF16X3)) {
-    set_error(std::string("math must be 0 (fp32)") + (bf16x3_ok ? ", DM_SPLIT_BF16X3" : "") + " or DM_SPLIT_FP16X2");
+  if (kind != 0 && kind != DM_SPLIT_FP16X2 && !(bf16x3_ok && kind == DM_SPLIT_BF16X3) &&
+      !(fp16_ok && kind == DM_MATH_FP16)) {
+    set_error(std::string("math must be 0 (fp32)") + (bf16x3_ok ? ", DM_SPLIT_BF16X3" : "") +
+              (fp16_ok ? ", DM_MATH_FP16" : "") + " or DM_SPLIT_FP16X2" +
+              (fp16_ok ? "" : " (DM_MATH_FP16 is for the token models, dm_dit_* / dm_mdt_*, only)"));
     return DM_ERR_ARG;
   }
   m->fallback = false;

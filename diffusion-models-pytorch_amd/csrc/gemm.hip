@@ -444,6 +444,7 @@ int linear_rows(const GemmArgs& g, hipStream_t st) {
 
 int gemm_batched(const GemmArgs& g, hipStream_t st) {
   DM_REQUIRE(g.M > 0 && g.N > 0 && g.K > 0, "gemm: empty problem");
+  if (g.h16) return linear_h16(g, st);  // DM_MATH_FP16: one fp16 product per MAC (linear_h16.hip)
   if (g.ws) return linear_k32(g, st);  // pre-split static weights (linear_k32.hip)
   DM_REQUIRE(g.K % 4 == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0, "gemm: K and leading dims must be multiples of 4");
   DM_REQUIRE(!g.b_kn || g.N % 4 == 0, "gemm: N must be a multiple of 4 for the [k][n] B layout");
@@ -472,6 +473,7 @@ int gemm_pick(const GemmArgs& g) {
 }
 
 std::string gemm_label(const GemmArgs& g) {
+  if (g.h16) return "linear_h16_kernel";
   if (g.ws) {
     return std::string("linear_k32_kernel<") + (g.as ? "3>" : g.pro_scale ? "1>" : g.ln_stats ? "2>" : "0>");
   }

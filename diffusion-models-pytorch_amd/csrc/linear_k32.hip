@@ -880,8 +880,11 @@ extern "C" int dm_debug_linear_k32(const float* A, int lda, const float* W, cons
  * 2: gemm.hip fp32 (the range fallback's arithmetic). a_form 0: prologue and split in the GEMM; 1: linear_presplit_a
  * into the caller's `as`, then (path 0) the GEMM on that image without a prologue -- gemm.hip has no pre-split
  * input: paths 1 / 2 write the image and run the GEMM as a_form 0; 2 (path 0): the caller's `as` as given.
- * A descriptor linear_k32_ok refuses (path 0), or a gemm.hip path asked for a linear_k32-only output, returns
- * DM_ERR_UNSUPPORTED and launches nothing. Synchronous. */
+ * path 3: linear_h16 (DM_MATH_FP16, linear_h16.hip) on piece 0 of the same split weights. a_form 0: linear_h16_image
+ * into a temporary, then the GEMM; 1: the image into the caller's `as` (one fp16 plane [M][K]), then the GEMM; 2: the
+ * GEMM on the caller's own plane. c_split is then a single plane [M][N]; sk is not built (DM_ERR_UNSUPPORTED).
+ * A descriptor linear_k32_ok / linear_h16_ok refuses (paths 0 / 3), or a gemm.hip path asked for a linear_k32-only
+ * output, returns DM_ERR_UNSUPPORTED and launches nothing. Synchronous. */
 struct dm_debug_gemm_desc {
   int M, N, K;
   int path, a_form, sk;
@@ -926,7 +929,7 @@ extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
     return DM_ERR_ARG;
   };
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0 || !d->W) return bad_arg("token gemm: empty problem");
-  if (d->path < 0 || d->path > 2 || d->a_form < 0 || d->a_form > 2) return bad_arg("token gemm: path 0..2, a_form 0..2");
+  if (d->path < 0 || d->path > 3 || d->a_form < 0 || d->a_form > 2) return bad_arg("token gemm: path 0..3, a_form 0..2");
   if (d->a_form != 2 && !d->A) return bad_arg("token gemm: A");
   if (d->a_form != 0 && !d->as) return bad_arg("token gemm: a_form 1 / 2 need the `as` buffer");
   if (!d->C && !d->c_split && !d->ap_q) return bad_arg("token gemm: no output");
@@ -942,8 +945,12 @@ extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
           d->ap_Dh > 0 && d->N == (d->ap_vonly ? C : 3 * C)))
       return bad_arg("token gemm: attention plane geometry");
   }
-  if (d->path != 0 && (d->a_form == 2 || d->c_split || d->ap_q || d->sk)) {
+  if (d->path != 0 && d->path != 3 && (d->a_form == 2 || d->c_split || d->ap_q || d->sk)) {
     set_error("token gemm: pre-split input, c_split, planes and split-K are linear_k32 forms");
+    return DM_ERR_UNSUPPORTED;
+  }
+  if (d->path == 3 && d->sk) {
+    set_error("token gemm: linear_h16 has no split-K tail");
     return DM_ERR_UNSUPPORTED;
   }
   GemmArgs g{};
@@ -961,6 +968,7 @@ extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
   g.ap_alpha = d->ap_alpha; g.ap_bscale = d->ap_bscale; g.ap_ea = d->ap_ea; g.ap_eb = d->ap_eb; g.ap_ev = d->ap_ev;
   g.range_flag = d->range_flag;
   void* ws = nullptr;
+  void* img = nullptr;
   float* skw = nullptr;
   unsigned* skc = nullptr;
   int rc = DM_OK;
@@ -970,6 +978,22 @@ extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
   };
   do {
     GemmArgs gp = g;  // the pre-split pass: the prologue, alpha and the split of A
+    if (d->path == 3) {
+      if (d->K % 64 != 0) { set_error("token gemm: linear_h16 needs K % 64 == 0"); rc = DM_ERR_UNSUPPORTED; break; }
+      if (hipMalloc(&ws, split_conv_weights_bytes(1, d->N, d->K, 2)) != hipSuccess) { rc = fail("alloc"); break; }
+      g.ws = ws; g.ws_rowscale = split_conv_rowscale(ws, 1, d->N, d->K);
+      g.h16 = 1;
+      if (d->a_form == 0 && hipMalloc(&img, (size_t)d->M * d->K * 2) != hipSuccess) { rc = fail("alloc"); break; }
+      g.as = (const _Float16*)(d->a_form == 0 ? img : d->as);
+      g.pro_scale = g.pro_shift = nullptr;   // the image pass applies the prologue
+      g.ln_stats = nullptr;
+      if (!linear_h16_ok(g)) { set_error("token gemm: linear_h16_ok refuses the descriptor"); rc = DM_ERR_UNSUPPORTED; break; }
+      if ((rc = split_conv_weights(d->W, 1, d->N, d->K, d->K, 1, 2, ws, st)) != DM_OK) break;
+      if (d->a_form != 2 && (rc = linear_h16_image(gp, (_Float16*)g.as, st)) != DM_OK) break;
+      if ((rc = gemm_batched(g, st)) != DM_OK) break;
+      if (hipStreamSynchronize(st) != hipSuccess) rc = fail("sync");
+      break;
+    }
     if (d->path == 0) {
       if (d->K % 64 != 0) { set_error("token gemm: linear_k32 needs K % 64 == 0"); rc = DM_ERR_UNSUPPORTED; break; }
       if (hipMalloc(&ws, split_conv_weights_bytes(1, d->N, d->K, 2)) != hipSuccess) { rc = fail("alloc"); break; }
@@ -1000,6 +1024,7 @@ extern "C" int dm_debug_token_gemm(const dm_debug_gemm_desc* d, void* stream) {
   } while (false);
   (void)hipStreamSynchronize(st);
   if (ws) (void)hipFree(ws);
+  if (img) (void)hipFree(img);
   if (skw) (void)hipFree(skw);
   if (skc) (void)hipFree(skc);
   return rc;

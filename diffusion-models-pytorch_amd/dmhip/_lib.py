@@ -535,6 +535,11 @@ def pack_conv_weight_subpixel(w: torch.Tensor, out: torch.Tensor):
 SPLIT_FP16X2 = 2  # DM_SPLIT_FP16X2
 SPLIT_BF16X3 = 3  # DM_SPLIT_BF16X3
 CONV_MATH = {'fp32': 0, 'fp16x2': SPLIT_FP16X2, 'bf16x3': SPLIT_BF16X3}
+MATH_FP16 = 1  # DM_MATH_FP16: one fp16 product per MAC in the token GEMMs of DiT / MDT (no fp32 parity)
+# every arithmetic a handle can report (range_stats); the UNet / VAE setters validate against CONV_MATH, the token
+# models against TOKEN_MATH
+MATH_NAMES = dict(CONV_MATH, fp16=MATH_FP16)
+TOKEN_MATH = {'fp32': 0, 'fp16x2': SPLIT_FP16X2, 'fp16': MATH_FP16}
 
 
 def pack_conv_weight_split(wp: torch.Tensor, nmat: int, Cin: int, taps: int, kind: int = SPLIT_BF16X3) -> torch.Tensor:
@@ -567,9 +572,12 @@ def pack_conv_weight_wino(wp: torch.Tensor, Cin: int, Cin2: int = 0, fold: bool 
 
 def dit_math(handle, kind: Optional[str] = None, abi: str = 'dm_dit') -> str:
     """Set (kind given) and return the GEMM arithmetic of a native DiT (abi 'dm_mdt': MDT) handle: 'fp16x2'
-    (default) or 'fp32' (dm_dit_set_math / dm_dit_get_math)."""
+    (default), 'fp32', or 'fp16' -- the opt-in half-precision mode: the static-weight token GEMMs round each operand
+    once to fp16 and spend one matrix-core product per MAC (fp32 accumulation and epilogues; attention, softmax,
+    statistics and the residual stream as in 'fp16x2'); faster, without fp32 parity (dm_dit_set_math /
+    dm_dit_get_math)."""
     L = load()
-    kinds = {'fp32': 0, 'fp16x2': SPLIT_FP16X2}
+    kinds = TOKEN_MATH
     if kind is not None:
         if kind not in kinds:
             raise ValueError(f'DiT math must be one of {sorted(kinds)}')
@@ -683,7 +691,7 @@ def range_stats(handle, abi: str = 'dm_unet'):
     model handle (dm_unet_range_stats / dm_dit_range_stats)."""
     n, active = ctypes.c_int64(), ctypes.c_int()
     check(getattr(load(), abi + '_range_stats')(handle, ctypes.byref(n), ctypes.byref(active)), abi + '_range_stats')
-    return n.value, {v: k for k, v in CONV_MATH.items()}[active.value]
+    return n.value, {v: k for k, v in MATH_NAMES.items()}[active.value]
 
 
 def plan_stats(handle, abi: str = 'dm_unet'):

@@ -51,6 +51,11 @@ class DiT(BaseLatent):
         z = 1. / self.scale_factor * z
         return self.vae.decode(z).sample
 
+    def set_math(self, kind: str) -> str:
+        """The arithmetic of the transformer's token GEMMs ('fp16x2', 'fp32' or the half-precision 'fp16':
+        ``models.dit.model.TokenMath.set_math``). The VAE keeps its own arithmetic."""
+        return self.vit.set_math(kind)
+
     def vit_forward(self, x: Tensor, t: Tensor, y: Tensor):
         return self.vit(x, t, y)
 

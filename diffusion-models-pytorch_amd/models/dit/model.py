@@ -28,8 +28,32 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from dmhip._lib import DiTArch, check, load, stream_handle
+from dmhip._lib import TOKEN_MATH, DiTArch, check, dit_math, load, stream_handle
 from ..unet import NativeDenoiser
+
+
+class TokenMath:
+    """``set_math`` of the native token models (DiT, MDTv2): the arithmetic of their token GEMMs, 'fp16x2'
+    (default, fp32-accurate), 'fp32', or 'fp16' (the opt-in half-precision mode of dm_dit_set_math: one fp16 product
+    per MAC in the static-weight GEMMs, faster, no fp32 parity). Applies to the native handle the model has and to
+    every handle it builds later (a parameter change or a move re-packs the model)."""
+
+    _math = None
+
+    def set_math(self, kind: str) -> str:
+        if kind not in TOKEN_MATH:
+            raise ValueError(f'math must be one of {sorted(TOKEN_MATH)}')
+        self._math = kind
+        if self._native is not None:
+            dit_math(self._native, kind, self._abi)
+        return kind
+
+    def native_handle(self, device: torch.device):
+        had = self._native
+        handle = super().native_handle(device)
+        if handle is not had and self._math is not None:
+            dit_math(handle, self._math, self._abi)
+        return handle
 
 
 def get_2d_sincos_pos_embed(embed_dim: int, grid_size: int) -> np.ndarray:
@@ -120,7 +144,7 @@ class FinalLayer(nn.Module):
         self.adaLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(hidden_size, 2 * hidden_size, bias=True))
 
 
-class DiT(NativeDenoiser):
+class DiT(TokenMath, NativeDenoiser):
     """Diffusion model with a Transformer backbone (model.py:145-270)."""
 
     _abi = 'dm_dit'

@@ -26,7 +26,8 @@ from torch import Tensor
 
 from dmhip._lib import MDTArch, check, load, stream_handle
 from ..unet import NativeDenoiser
-from ..dit.model import FinalLayer, LabelEmbedder, Mlp, PatchEmbed, TimestepEmbedder, get_2d_sincos_pos_embed
+from ..dit.model import (FinalLayer, LabelEmbedder, Mlp, PatchEmbed, TimestepEmbedder, TokenMath,
+                         get_2d_sincos_pos_embed)
 
 
 def relative_position_index(W: int) -> Tensor:
@@ -79,7 +80,7 @@ class MDTBlock(nn.Module):
         self.skip_linear = nn.Linear(2 * hidden_size, hidden_size) if skip else None
 
 
-class MDTv2(NativeDenoiser):
+class MDTv2(TokenMath, NativeDenoiser):
     """Masked Diffusion Transformer v2 (mdt/model.py:246-526), inference path."""
 
     _abi = 'dm_mdt'

@@ -27,6 +27,9 @@ checkpoint directory in the diffusers layout (config.json +
 diffusion_pytorch_model.safetensors or .bin) and the script writes PNGs. The
 YAML's default is a hub id, which is never fetched: without a local directory
 the clamp-free latents are written as `{idx}.npy` (float32 [4, S, S]) instead.
+
+`--math {fp16x2,fp32,fp16}` (not in the reference) selects the arithmetic of a DiT / MDT denoiser's token GEMMs;
+`fp16` is the engine's half-precision mode (one fp16 product per MAC, no fp32 parity). Other models refuse it.
 """
 import argparse
 import math
@@ -62,6 +65,9 @@ def get_parser():
     p.add_argument('--var_type', type=str, default=None)
     p.add_argument('--ddim_eta', type=float, default=0.0)
     p.add_argument('--shard', action='store_true', help='shard each fold across ranks (not reference behaviour)')
+    p.add_argument('--math', type=str, choices=['fp16x2', 'fp32', 'fp16'], default=None,
+                   help="arithmetic of a DiT / MDT denoiser's token GEMMs (default: the engine's, fp16x2); 'fp16' is "
+                        "the half-precision mode: faster, no fp32 parity")
     return p
 
 
@@ -90,6 +96,11 @@ def main(argv=None):
     env = DistEnv()
     torch.manual_seed(args.seed + env.rank)
     model = build_model(conf, args.weights, env.device)
+    if args.math is not None:
+        if not hasattr(model, 'set_math'):
+            raise SystemExit(f'--math selects the arithmetic of the token GEMMs of DiT / MDT; '
+                             f'{type(model).__name__} has no token path')
+        model.set_math(args.math)
     latent = isinstance(model, BaseLatent)
     diffuser = build_cfg_diffuser(args, conf, env.device, latent=latent)
     size = conf.data.params.img_size

@@ -181,7 +181,19 @@ int dm_dit_create(const dm_dit_arch* arch, const float* const* params, const int
 int dm_dit_forward(dm_dit* m, const float* x, const int64_t* t, const int64_t* y, int B, float* out, void* stream);
 /* Arithmetic of the DiT token GEMMs: DM_SPLIT_FP16X2 (default, fp32-accurate products from an fp16 split
  * on the matrix cores) or 0 (fp32 MFMA; also DM_CONV_MATH=fp32|bf16x3). A forward whose operands leave
- * the fp16 range is re-run in fp32; the next forward is fp16x2 again. */
+ * the fp16 range is re-run in fp32; the next forward is fp16x2 again.
+ *
+ * DM_MATH_FP16 (opt-in, the token models dm_dit_* / dm_mdt_* only; not an fp32-parity mode): the static-weight
+ * token GEMMs (qkv, proj, fc1, fc2, MDT's skip_linear, the final layer) round each operand ONCE to fp16 --
+ * a' = fp16(prologue(a) * 2^6), w' = fp16(w * 2^er(row)), the high piece of the fp16x2 split -- and spend one
+ * matrix-core product per MAC with fp32 accumulation (fp16x2 spends three); the epilogues stay fp32. What it is
+ * not: the residual stream, LayerNorm statistics, adaLN tables (and their GEMM), softmax, patch embedding,
+ * timestep / label embedding and the attention products S = q k^T, P v keep the fp16x2 mode's arithmetic; a
+ * GEMM the half-precision kernel refuses runs as in fp16x2. Each rounding is 2^-11 relative, so outputs differ
+ * from the fp32 reference at the 1e-3 level of the activations (DESIGN.md 4.18 has measured figures). The range
+ * guard is the fp16x2 one: a flagged forward is re-run in fp32, counted once, and the next one is fp16 again.
+ * DM_CONV_MATH does not select this mode; the conv nets (dm_unet_*, the VAEs) reject it. */
+#define DM_MATH_FP16 1
 int dm_dit_set_math(dm_dit* m, int kind);
 int dm_dit_get_math(const dm_dit* m, int* kind);
 /* As dm_unet_set_range_deferred / dm_unet_range_poll / _range_fallback / _range_stats (the DiT's fallback
@@ -234,6 +246,9 @@ int dm_mdt_param_count(const dm_mdt_arch* arch, int* n_params);
 int dm_mdt_create(const dm_mdt_arch* arch, const float* const* params, const int64_t* numels, int n_params,
                   void* stream, dm_mdt** out);
 int dm_mdt_forward(dm_mdt* m, const float* x, const int64_t* t, const int64_t* y, int B, float* out, void* stream);
+/* As dm_dit_set_math: DM_SPLIT_FP16X2 (default), 0 (fp32) or DM_MATH_FP16 (one fp16 product per MAC in the
+ * static-weight token GEMMs, skip_linear included; attention, softmax, statistics and the residual stream as in
+ * fp16x2 -- a throughput mode without fp32 parity). */
 int dm_mdt_set_math(dm_mdt* m, int kind);
 int dm_mdt_get_math(const dm_mdt* m, int* kind);
 int dm_mdt_set_range_deferred(dm_mdt* m, int deferred);

@@ -1,5 +1,6 @@
 """MDT-XL/2 against DiT-XL/2: forward time at the CFG batch 2B = 64 (4x32x32 latents), both models in one process,
-alternating, plus the per-launch time of the biased flash attention kernel (MDT) against the unbiased one (DiT) on the
+alternating, each in the default fp16x2 arithmetic and in 'fp16' (DM_MATH_FP16: one fp16 product per MAC, no fp32
+parity; its own model object and plan, so the alternation rebuilds nothing), plus the per-launch time of the biased flash attention kernel (MDT) against the unbiased one (DiT) on the
 same (64 * 16, 256, 72) operand shape, from the plans' own per-launch profiles (dm_mdt_profile / dm_dit_profile).
 
     python tools/mdt_bench.py [--batch 64] [--iters 10] [--rounds 3] [--json out.json]
@@ -64,9 +65,11 @@ def main():
     args = (torch.randn((B, 4, 32, 32), generator=g).to(dev), torch.randint(0, 1000, (B, ), generator=g).to(dev),
             torch.randint(0, 1000, (B, ), generator=g).to(dev))
     models = {}
-    for name, f in (('DiT-XL/2', DiT_XL_2), ('MDT-XL/2', MDTv2_XL_2)):
+    for name, f, math in (('DiT-XL/2', DiT_XL_2, 'fp16x2'), ('MDT-XL/2', MDTv2_XL_2, 'fp16x2'),
+                          ('DiT-XL/2 fp16', DiT_XL_2, 'fp16'), ('MDT-XL/2 fp16', MDTv2_XL_2, 'fp16')):
         m = f(input_size=32, num_classes=1000, learn_sigma=True).eval()
         init_synthetic_(m)
+        m.set_math(math)
         models[name] = m.to(dev)
         for _ in range(3):   # plan build, graph capture, warm-up
             models[name](*args)
@@ -77,12 +80,17 @@ def main():
             res[name].append(timed(m, args, a.iters))
     out = dict(batch=B, iters=a.iters, device=torch.cuda.get_device_name(0), forward_ms=res)
     for name, v in res.items():
-        print(f'{name} B={B}: ' + ' '.join(f'{x:.2f}' for x in v) + f' ms/forward (min {min(v):.2f})', flush=True)
+        print(f'{name} B={B}: ' + ' '.join(f'{x:.2f}' for x in v) + f' ms/forward (min {min(v):.2f}, spread '
+              f'{(max(v) - min(v)) / min(v) * 100:.1f} %)', flush=True)
+    for name in ('DiT-XL/2', 'MDT-XL/2'):
+        out[f'{name} fp16x2_over_fp16'] = min(res[name]) / min(res[name + ' fp16'])
+        print(f'{name}: fp16x2 / fp16 = x{out[name + " fp16x2_over_fp16"]:.3f}')
     ratio = min(res['MDT-XL/2']) / min(res['DiT-XL/2'])
     out['mdt_over_dit'] = ratio
     print(f'MDT-XL/2 / DiT-XL/2 = {ratio:.3f} (derived from block and skip-GEMM counts: ~1.10)')
     prof = {'DiT-XL/2': profile(models['DiT-XL/2'], 'dm_dit', args, 3),
-            'MDT-XL/2': profile(models['MDT-XL/2'], 'dm_mdt', args, 3)}
+            'MDT-XL/2': profile(models['MDT-XL/2'], 'dm_mdt', args, 3),
+            'MDT-XL/2 fp16': profile(models['MDT-XL/2 fp16'], 'dm_mdt', args, 3)}
     out['profile'] = prof
     for name, p in prof.items():
         tot = sum(v['ms_total'] for v in p.values()) / 3
