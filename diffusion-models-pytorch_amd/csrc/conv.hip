@@ -284,6 +284,7 @@ int conv2d_igemm(const ConvArgs& a, hipStream_t st) {
   }
   const long M = (long)a.B * a.Hout * a.Wout;
   DM_REQUIRE(M > 0 && M < (1L << 31), "conv: M out of range");
+  if (a.h16) return conv2d_h16(a, st);  // a conv the plan marked for the conv-half kernel (conv_h16.hip)
   DM_REQUIRE(a.tile >= 0 && a.tile <= 22, "conv: tile must be 0..22");
   if (a.tile == 21 || (a.tile == 0 && a.wino_ws)) {  // the Winograd F(2,3) kernel (conv_wino.hip)
     if (conv_wino_ok(a)) {
@@ -357,6 +358,7 @@ int conv_pick(const ConvArgs& a) {
 }
 
 bool conv_can_emit_gn(const ConvArgs& a) {
+  if (a.h16) return conv_h16_can_emit(a);  // the conv-half kernel: StagedEpilogue over each wave's 64-pixel chunk
   // the split-K reduction emits them (conv_splitk_reduce_gn_kernel; after the 4 x 4 Winograd kernel, conv_k32s's own
   // in-block reduction): one chunk per image
   if (a.ksplit > 1)
@@ -396,6 +398,7 @@ std::string conv_label(const ConvArgs& a) {
                                 "conv_patch_kernel<128,64,64,32",  "conv_patch_kernel<64,64,32,32",
                                 "conv_patch_kernel<256,256,128,128", "conv_patch_kernel<512,128,128,128",
                                 "conv_patch_kernel<128,128,64,64"};
+  if (a.h16) return conv_h16_label(a);
   if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a)) return conv_wino_label(a);
   if (const int k32 = a.k32_resolved ? a.k32_resolved - 1 : conv_k32_pick(a)) return conv_k32_label(a, k32);
   const int p = conv_pick(a);

@@ -139,6 +139,13 @@ struct ConvArgs {
   // op's profile label come from one decision
   int k32_resolved;
   int s2_pad0;  // 1: stride-2 taps start at 2o (input padded bottom/right only); 0: at 2o - 1 (padding 1)
+  // the conv-half option of the UNet plans (conv_h16.hip): h16 = 1 marks a conv conv_h16_ok takes in
+  // a plan with the switch on (ExecNet::split_for); such a conv runs conv_h16_image (prologue, one rounding to fp16:
+  // the plane h16_a1 [B][Hin][Win][Cin1], and h16_a2 [B][Hout][Wout][Cin2] of x2) and then conv_h16_kernel on the
+  // planes and piece 0 of `ws`. pro_scale / pro_shift belong to the image pass; gin_* and wino_ws are not used.
+  int h16;
+  const _Float16* h16_a1;
+  const _Float16* h16_a2;
 };
 
 // Patch-pixel capacity of the halo-patch kernels' LDS images (fp32 / split-bf16; 128- / 64-row tiles)
@@ -365,6 +372,20 @@ int linear_h16(const GemmArgs& g, hipStream_t st);
 int linear_h16_image(const GemmArgs& g, _Float16* out, hipStream_t st);
 int linear_h16_image_cat(const float* x, const float* skip, long M, int D, int ea, _Float16* out, int* range_flag,
                          hipStream_t st);
+// The conv-half option (conv_h16.hip): 3x3 stride-1 convs with ONE v_mfma_f32_16x16x32_f16 product per MAC on
+// a' = fp16_rne(prologue(x1)), a2' = fp16_rne(x2) and piece 0 of the fp16x2 fragment image in `ws`, fp32 accumulation,
+// the fp32 epilogue of conv_k32. conv_h16_ok is the single gate (shape, alignment, the staged epilogue's rules; the
+// planes, where set, 16-byte aligned); conv_h16_form the tile form a conv runs in (1: 128 x 128 tiles of whole rows
+// of 8- / 16- / 32-wide maps, two 8 x 8 images per tile; 2: 4 x 32-pixel 2-D tiles of 64- .. 256-wide maps; 0: none;
+// ConvArgs::tile 0 picks, 1 / 2 force). conv_h16_image writes the plane(s) and raises range_flag beyond 65504;
+// conv2d_h16 launches the kernel on ConvArgs::h16_a1 / h16_a2. conv_h16_can_emit: the GroupNorm partials rule of its
+// StagedEpilogue (conv_can_emit_gn answers with it for a conv marked h16).
+bool conv_h16_ok(const ConvArgs& a);
+int conv_h16_form(const ConvArgs& a);
+bool conv_h16_can_emit(const ConvArgs& a);
+int conv_h16_image(const ConvArgs& a, _Float16* plane1, _Float16* plane2, hipStream_t st);
+int conv2d_h16(const ConvArgs& a, hipStream_t st);
+std::string conv_h16_label(const ConvArgs& a);
 int conv_splitk_reduce(const ConvArgs& a, hipStream_t st);
 // fp32 packed conv weights [nmat][rows][K] -> split slices for conv_patch3_kernel (np 3: bf16x3,
 // np 2: fp16x2 + row scales); split_conv_rowscale gives ConvArgs::ws_rowscale of an fp16x2 copy

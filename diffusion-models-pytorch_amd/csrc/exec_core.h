@@ -54,6 +54,12 @@ struct ExecNet {
   // the UNet plans put the Winograd kernel on 4 x 4 maps (a split-K form, where maybe_split chose wino_small_ks
   // splits); the other networks keep the direct kernel there
   bool wino_small = false;
+  // The conv-half option of the conv UNets (dm_unet_set_conv_half), a switch beside the arithmetic, not
+  // a fourth kind of it: in a plan of the fp16x2 arithmetic the 3x3 stride-1 convs conv_h16_ok takes run with one fp16
+  // product per MAC (conv_h16.hip). base_math keeps governing everything else and stays the range fallback's source;
+  // fp32 / bf16x3 plans (the fallback's included) are unchanged. Off by default; the other networks never set it.
+  bool conv_half = false;
+  bool half_active() const { return conv_half && conv_math == DM_SPLIT_FP16X2; }
 
   ExecNet() = default;
   ExecNet(const ExecNet&) = delete;
@@ -92,6 +98,7 @@ struct ExecNet {
   // row-segment tile beyond; the pesser UNet's Downsample), and only then: no split copy is made for a conv that
   // stays on im2col.
   void split_for(ConvArgs& c) {
+    c.h16 = 0;
     c.ws = nullptr;
     c.ws_np = 0;
     c.ws_rowscale = nullptr;
@@ -135,6 +142,16 @@ struct ExecNet {
     if (conv_math == 2) {
       c.ws_rowscale = split_conv_rowscale(p, nmat, c.Cout, c.K);
       c.range_flag = range_flag;
+    }
+    // conv-half plans: a covered conv that got its fp16x2 copy is marked for conv_h16 (conv_h16.hip) and takes no
+    // Winograd weights; a conv the gate refuses runs as in fp16x2
+    if (half_active()) {
+      ConvArgs t = c;
+      t.gn_part = nullptr;  // (the statistics rule is conv_can_emit_gn's, asked by the plan)
+      if (conv_h16_ok(t)) {
+        c.h16 = 1;
+        return;
+      }
     }
     // the Winograd F(2,3) kernel for the 3x3 convs it takes (DM_CONV_WINO=0: conv_k32, its test oracle)
     if (conv_math != 2 || !toggles().wino || !conv_wino_shape_ok(c)) return;

@@ -102,6 +102,7 @@ struct UNetModel : ExecNet {
   struct Plan : PlanBase {
     int B = 0, H = 0, W = 0;
     int math = 0;   // the arithmetic the plan was built with (conv_math at build time)
+    bool half = false;  // built with the conv-half option in effect (an fp16x2 plan of a model with conv_half set)
     // plan-owned staging of the caller's tensors (every launch reads fixed pointers: graph replay)
     float* x = nullptr;
     int64_t* t = nullptr;
@@ -126,7 +127,8 @@ struct UNetModel : ExecNet {
   int build_plan(Plan& pl, int B, int H, int W);
   int get_plan(int B, int H, int W, int math, Plan** out) {
     conv_math = math;
-    return plans.get([&](const Plan& p) { return p.B == B && p.H == H && p.W == W && p.math == math; },
+    const bool half = half_active();
+    return plans.get([&](const Plan& p) { return p.B == B && p.H == H && p.W == W && p.math == math && p.half == half; },
                      [&](Plan& p) { return build_plan(p, B, H, W); }, out);
   }
 };
@@ -581,6 +583,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   pl.graph_enabled = toggles().graph;
   pl.B = B;
   pl.math = conv_math;
+  pl.half = half_active();
   pl.H = H;
   pl.W = W;
   if (const int rcf = ensure_range_flag()) return rcf;
@@ -640,6 +643,23 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   for (auto& n : nodes) max_c = std::max(max_c, (size_t)std::max(n.cin, n.cout));
   float* gsc = alloc((size_t)B * max_c * 4);
   float* gsh = alloc((size_t)B * max_c * 4);
+  // conv-half plans: the fp16 image planes of the covered convs' two segments (conv_h16_image), the largest once.
+  // Only ResBlock convs can be covered (conv1: Cin1 = cin; conv2: Cin1 = cout, Cin2 = cin where the widths differ), at
+  // the block's output resolution and on maps of >= 64 pixels: sized from those. add_conv checks every use against it.
+  _Float16* h16_p1 = nullptr;
+  _Float16* h16_p2 = nullptr;
+  size_t h16_cap1 = 0, h16_cap2 = 0;  // fp16 elements
+  bool h16_overflow = false;
+  if (pl.half) {
+    for (auto& n : nodes) {
+      const size_t hw_o = (size_t)Hl(n.level_out) * Wl(n.level_out);
+      if (n.kind != N_RES || hw_o < 64) continue;
+      h16_cap1 = std::max(h16_cap1, (size_t)B * hw_o * std::max(n.cin, n.cout));
+      if (n.cin != n.cout) h16_cap2 = std::max(h16_cap2, (size_t)B * hw_o * n.cin);
+    }
+    if (h16_cap1) h16_p1 = (_Float16*)alloc(h16_cap1 * 2);
+    if (h16_cap2) h16_p2 = (_Float16*)alloc(h16_cap2 * 2);
+  }
 
   // --- concat buffers for up-RBs and skip slot views
   std::vector<View> skip_view(skip_C.size());
@@ -704,6 +724,24 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
   auto add_conv = [&](ConvArgs c) {
     maybe_split(c);
     split_for(c);
+    if (c.h16) {  // conv-half: the image pass (prologue, one rounding), then conv_h16_kernel
+      const size_t need1 = (size_t)c.B * c.Hin * c.Win * c.Cin1, need2 = (size_t)c.B * c.Hout * c.Wout * c.Cin2;
+      if (c.gin_part || need1 > h16_cap1 || need2 > h16_cap2) {  // (gn_prologue keeps gin_* off a marked conv)
+        h16_overflow = true;
+        return;
+      }
+      c.h16_a1 = h16_p1;
+      c.h16_a2 = c.Cin2 ? h16_p2 : nullptr;
+      c.k32_resolved = 0;
+      double fl, by;
+      conv_cost(c, fl, by);
+      const double npix = (double)c.B * c.Hin * c.Win;
+      add("conv_h16_image", 0, 6.0 * npix * (c.Cin1 + c.Cin2), [=](hipStream_t st) {
+        return conv_h16_image(c, const_cast<_Float16*>(c.h16_a1), const_cast<_Float16*>(c.h16_a2), st);
+      });
+      add(conv_label(c), fl, by - 2.0 * npix * (c.Cin1 + c.Cin2), [=](hipStream_t st) { return conv2d_h16(c, st); });
+      return;
+    }
     c.k32_resolved = 1 + conv_k32_pick(c);  // one decision for the launch and the label
     double fl, by;
     conv_cost(c, fl, by);
@@ -863,7 +901,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     }();
     // in-kernel finalize: every block re-reduces its images' chunk partials, so only for small maps
     // (CIFAR: <= 16 chunks per image); the 256^2 maps of ADM have 1024 and take the finalize launch
-    if (conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
+    if (!c.h16 && conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
       c.gin_part = stp; c.gin_G = G; c.gin_nchunk = gn_num_chunks(v.H * v.W);
       c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = gn_eps;
       c.gin_gamma = P(gamma); c.gin_beta = P(beta); c.gin_ms = ms; c.gin_mb = mb; c.gin_mp = mp;
@@ -1283,6 +1321,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
                           : conv3x3_small_out(xin, lw, lb, oc, P_->out, st, gsc, gsh);
         });
   }
+  DM_REQUIRE(!h16_overflow, "conv-half plan: a covered conv with in-kernel GroupNorm tables, or beyond the image planes");
   return DM_OK;
 }
 
@@ -1387,6 +1426,23 @@ extern "C" int dm_unet_plan_stats(const dm_unet* h, int64_t* builds, int* cached
 }
 extern "C" int dm_unet_set_conv_math(dm_unet* h, int kind) { return dm::abi_set_math(dm::model_of(h), kind, true); }
 extern "C" int dm_unet_get_conv_math(const dm_unet* h, int* kind) { return dm::abi_get_math(dm::model_of(h), kind); }
+
+extern "C" int dm_unet_set_conv_half(dm_unet* h, int on) {
+  auto* m = dm::model_of(h);
+  DM_ABI_MODEL(m);
+  if (on != 0 && on != 1) { dm::set_error("conv_half must be 0 or 1"); return DM_ERR_ARG; }
+  if ((on != 0) != m->conv_half) {
+    m->conv_half = on != 0;
+    m->plans.clear();
+  }
+  return DM_OK;
+}
+extern "C" int dm_unet_get_conv_half(const dm_unet* h, int* on) {
+  auto* m = dm::model_of(h);
+  DM_ABI_MODEL(m && on);
+  *on = m->conv_half ? 1 : 0;
+  return DM_OK;
+}
 extern "C" int dm_unet_set_time_freqs(dm_unet* h, const float* freqs, int n, void* stream) {
   return dm::abi_set_time_freqs(dm::model_of(h), freqs, n, (hipStream_t)stream);
 }

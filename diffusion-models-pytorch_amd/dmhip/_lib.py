@@ -286,6 +286,12 @@ def _declare(L: ctypes.CDLL):
                                             ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_unet_set_conv_math.argtypes = [vp, ctypes.c_int]
     L.dm_unet_get_conv_math.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    if hasattr(L, 'dm_unet_set_conv_half'):   # (absent from an older build under DM_HIP_LIB: tools/unet_bench.py's A/B arm)
+        L.dm_unet_set_conv_half.argtypes = [vp, ctypes.c_int]
+        L.dm_unet_get_conv_half.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+        L.dm_debug_conv_h16_image.argtypes = [ctypes.POINTER(ConvDesc), vp, vp]
+        L.dm_debug_conv_h16.argtypes = [ctypes.POINTER(ConvDesc), vp, ctypes.c_int, vp]
+        L.dm_debug_conv_h16_gn.argtypes = [ctypes.POINTER(ConvDesc), vp, ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_unet_set_range_deferred.argtypes = [vp, ctypes.c_int]
     L.dm_unet_range_poll.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int)]
     L.dm_unet_range_fallback.argtypes = [vp, ctypes.c_int]
@@ -611,6 +617,19 @@ def unet_conv_math(handle, kind: Optional[str] = None) -> str:
     k = ctypes.c_int()
     check(L.dm_unet_get_conv_math(handle, ctypes.byref(k)), 'dm_unet_get_conv_math')
     return {v: n for n, v in CONV_MATH.items()}[k.value]
+
+
+def unet_conv_half(handle, on: Optional[bool] = None) -> bool:
+    """Set (on given) and return the conv-half option of a native UNet handle (dm_unet_set_conv_half /
+    dm_unet_get_conv_half): with it on, plans of the 'fp16x2' arithmetic run their covered 3x3 stride-1 convs with one
+    fp16 product per MAC (operands rounded once, fp32 accumulation); everything else, and every other arithmetic, is
+    unchanged. Off by default; faster, without fp32 parity. Setting a different value drops the cached plans."""
+    L = load()
+    if on is not None:
+        check(L.dm_unet_set_conv_half(handle, 1 if on else 0), 'dm_unet_set_conv_half')
+    k = ctypes.c_int()
+    check(L.dm_unet_get_conv_half(handle, ctypes.byref(k)), 'dm_unet_get_conv_half')
+    return bool(k.value)
 
 
 def conv2d_nhwc(desc: ConvDesc, device=None):

@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from ..unet import NativeDenoiser
+from ..unet import ConvHalf, NativeDenoiser
 
 
 def _gn(C: int) -> nn.GroupNorm:
@@ -79,7 +79,7 @@ class Upsample(nn.Module):
             self.conv = nn.Conv2d(channels, out_channels or channels, 3, padding=1)
 
 
-class UNetModel(NativeDenoiser):
+class UNetModel(ConvHalf, NativeDenoiser):
     """The full ADM UNet with attention and timestep embedding (adm/unet.py:415-682)."""
 
     def __init__(self, image_size, in_channels, model_channels, out_channels, num_res_blocks,

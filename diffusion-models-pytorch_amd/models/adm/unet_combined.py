@@ -31,6 +31,11 @@ class UNetCombined(nn.Module):
         unet = self.unet_uncond if y is None else self.unet_cond
         return unet(x, timesteps, y)
 
+    def set_conv_half(self, on: bool = True) -> bool:
+        """The engine's opt-in conv-half option on both networks (``models.unet.ConvHalf``)."""
+        self.unet_cond.set_conv_half(on)
+        return self.unet_uncond.set_conv_half(on)
+
     def combine_weights(self, cond_path, uncond_path, save_path):
         """Merge two single-model checkpoints (tensor-only loads) into one combined state_dict."""
         self.unet_cond.load_state_dict(torch.load(cond_path, map_location='cpu', weights_only=True))

@@ -20,7 +20,7 @@ from typing import Sequence
 import torch.nn as nn
 from torch import Tensor
 
-from ..unet import NativeDenoiser
+from ..unet import ConvHalf, NativeDenoiser
 
 
 def _gn(C: int) -> nn.GroupNorm:
@@ -74,7 +74,7 @@ class Resample(nn.Module):
         self.conv = _conv(C, C, 3, stride=2, padding=0) if down else _conv(C, C, 3)
 
 
-class Model(NativeDenoiser):
+class Model(ConvHalf, NativeDenoiser):
     def __init__(self, *, ch: int, out_ch: int, ch_mult: Sequence[int] = (1, 2, 4, 8), num_res_blocks: int,
                  attn_resolutions: Sequence[int], dropout: float = 0.0, resamp_with_conv: bool = True,
                  in_channels: int, resolution: int):

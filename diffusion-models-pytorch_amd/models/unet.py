@@ -231,7 +231,31 @@ class NativeDenoiser(nn.Module):
         self._labels_ok = key
 
 
-class UNet(NativeDenoiser):
+class ConvHalf:
+    """``set_conv_half`` of the native conv denoisers (UNet, UNetCategorialAdaGN, ADM's UNetModel / UNetCombined, the
+    pesser Model): the engine's opt-in conv-half option (dm_unet_set_conv_half) -- in the default 'fp16x2' arithmetic
+    the covered 3x3 stride-1 convs spend one fp16 matrix-core product per MAC instead of three (operands rounded once
+    to fp16, fp32 accumulation and epilogue), faster, without fp32 parity. Not an option of the reference. Applies to
+    the native handle the model has and to every handle it builds later (a parameter change or a move re-packs the
+    model). The token models have ``set_math('fp16')`` instead."""
+
+    _conv_half = None
+
+    def set_conv_half(self, on: bool = True) -> bool:
+        self._conv_half = bool(on)
+        if self._native is not None:
+            dmhip.unet_conv_half(self._native, self._conv_half)
+        return self._conv_half
+
+    def native_handle(self, device: torch.device):
+        had = self._native
+        handle = super().native_handle(device)
+        if handle is not had and self._conv_half is not None:
+            dmhip.unet_conv_half(handle, self._conv_half)
+        return handle
+
+
+class UNet(ConvHalf, NativeDenoiser):
     def __init__(
             self,
             in_channels: int = 3,

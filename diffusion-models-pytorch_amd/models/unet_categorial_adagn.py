@@ -27,7 +27,7 @@ from typing import List
 import torch.nn as nn
 from torch import Tensor
 
-from .unet import NativeDenoiser, SelfAttentionBlock, _TimeEmbedding, _conv, _gn
+from .unet import ConvHalf, NativeDenoiser, SelfAttentionBlock, _TimeEmbedding, _conv, _gn
 
 
 class AdaGN(nn.Module):
@@ -64,7 +64,7 @@ class ResBlockDownsample(ResBlock):
         super().__init__(in_channels, out_channels, embed_dim, dropout, down=True)
 
 
-class UNetCategorialAdaGN(NativeDenoiser):
+class UNetCategorialAdaGN(ConvHalf, NativeDenoiser):
     """UNet conditioned on categorial labels with AdaGN (unet_categorial_adagn.py:75-208)."""
 
     supports_null_label = True  # y[b] = -1 = no label for row b (batched CFG, dmhip.null_label_scope)

@@ -30,6 +30,8 @@ the clamp-free latents are written as `{idx}.npy` (float32 [4, S, S]) instead.
 
 `--math {fp16x2,fp32,fp16}` (not in the reference) selects the arithmetic of a DiT / MDT denoiser's token GEMMs;
 `fp16` is the engine's half-precision mode (one fp16 product per MAC, no fp32 parity). Other models refuse it.
+`--conv_half` (not in the reference either) is the conv UNets' counterpart (`set_conv_half`: one fp16 product per MAC
+in the covered 3x3 convs); on a DiT / MDT model it exits with a pointer to `--math fp16`.
 """
 import argparse
 import math
@@ -43,7 +45,7 @@ import torch  # noqa: E402
 
 import diffusions  # noqa: E402
 from models.base_latent import BaseLatent  # noqa: E402
-from scripts.sample_uncond import build_model  # noqa: E402
+from scripts.sample_uncond import apply_conv_half, build_model  # noqa: E402
 from utils.harness import DistEnv, per_process_batch  # noqa: E402
 from utils.misc import amortize, image_norm_to_float, load_config  # noqa: E402
 from utils.png import save_image  # noqa: E402
@@ -68,6 +70,9 @@ def get_parser():
     p.add_argument('--math', type=str, choices=['fp16x2', 'fp32', 'fp16'], default=None,
                    help="arithmetic of a DiT / MDT denoiser's token GEMMs (default: the engine's, fp16x2); 'fp16' is "
                         "the half-precision mode: faster, no fp32 parity")
+    p.add_argument('--conv_half', action='store_true',
+                   help="the engine's conv-half option (not in the reference): one fp16 product per MAC in the covered 3x3 "
+                        "convs of a conv UNet; faster, no fp32 parity")
     return p
 
 
@@ -96,6 +101,7 @@ def main(argv=None):
     env = DistEnv()
     torch.manual_seed(args.seed + env.rank)
     model = build_model(conf, args.weights, env.device)
+    apply_conv_half(model, args.conv_half)
     if args.math is not None:
         if not hasattr(model, 'set_math'):
             raise SystemExit(f'--math selects the arithmetic of the token GEMMs of DiT / MDT; '

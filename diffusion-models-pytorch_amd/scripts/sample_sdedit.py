@@ -9,6 +9,9 @@ plus `--a.b value` config overrides and `--weights synthetic`:
 Each input is resized to img_size x img_size, noised to the `edit_steps`-th timestep of the (respaced) sequence with
 q(x_t | x_0) and denoised back with the DDPM reverse process; each output PNG is the row [input, noised, edited], as
 the reference writes it.
+
+`--conv_half` (not a reference option) turns on the engine's conv-half option (`set_conv_half`): one fp16 product per
+MAC in the covered 3x3 convs; faster, without fp32 parity.
 """
 import argparse
 import os
@@ -21,7 +24,7 @@ import tqdm  # noqa: E402
 
 import diffusions  # noqa: E402
 from scripts.sample_mask_guidance import diffusion_params, parse  # noqa: E402
-from scripts.sample_uncond import build_model  # noqa: E402
+from scripts.sample_uncond import apply_conv_half, build_model  # noqa: E402
 from utils.harness import DistEnv, dataset_rounds  # noqa: E402
 from utils.imagedir import ImageDir, resize_square_normalize  # noqa: E402
 from utils.png import save_image  # noqa: E402
@@ -39,6 +42,14 @@ def get_parser():
     p.add_argument('--input_dir', type=str, required=True, help='Path to the input directory')
     p.add_argument('--save_dir', type=str, required=True, help='Path to the directory to save samples')
     p.add_argument('--batch_size', type=int, default=32, help='Batch size on each process')
+    return p
+
+
+def engine_options(p):
+    """The engine's own options on top of the reference's CLI (get_parser stays the reference's, option for option)."""
+    p.add_argument('--conv_half', action='store_true',
+                   help="the engine's conv-half option (not in the reference): one fp16 product per MAC in the covered 3x3 "
+                        "convs of a conv UNet; faster, no fp32 parity")
     return p
 
 
@@ -78,13 +89,14 @@ def sdedit_fold(diffuser, model, img, edit_steps: int, tqdm_kwargs=None):
 
 @torch.no_grad()
 def main(argv=None):
-    args, conf = parse(get_parser(), argv)
+    args, conf = parse(engine_options(get_parser()), argv)
     env = DistEnv()
     torch.manual_seed(args.seed + env.rank)   # set_seed(seed, device_specific=True)
     diffuser = diffusions.ddpm.DDPM(**diffusion_params(args, conf, env.device))
     edit_time_seq(diffuser, args.edit_steps)   # fail before anything is built
     dataset = ImageDir(args.input_dir, conf.data.params.img_size, transform=resize_square_normalize)
     model = build_model(conf, args.weights, env.device)
+    apply_conv_half(model, args.conv_half)
     os.makedirs(args.save_dir, exist_ok=True)
     if len(dataset) == 0:
         raise ValueError(f'no images found in {args.input_dir}')

@@ -15,6 +15,9 @@ reconstruction (DDIM inversion of the images under --input_dir, then sampling ba
 Latent denoisers (the DiT config) are sampled by scripts/sample_cfg.py, which builds its model with this
 script's `build_model`: the override `--model.params.vae_config.params.from_pretrained /path/to/dir` (a local
 diffusers-layout VAE directory) is all it takes for decoded PNGs; there is no new flag.
+
+`--conv_half` (not a reference option) turns on the engine's conv-half option of a conv UNet (`set_conv_half`): the
+covered 3x3 convs spend one fp16 matrix-core product per MAC; faster, without fp32 parity.
 """
 import argparse
 import math
@@ -53,6 +56,9 @@ def get_parser():
     p.add_argument('--n_progressive', type=int, default=20)
     p.add_argument('--n_interpolate', type=int, default=16, help='Number of intermediate images (interpolate)')
     p.add_argument('--input_dir', type=str, required=False, help='Directory of images (reconstruction)')
+    p.add_argument('--conv_half', action='store_true',
+                   help="the engine's conv-half option (not in the reference): one fp16 product per MAC in the covered 3x3 "
+                        "convs of a conv UNet; faster, no fp32 parity")
     return p
 
 
@@ -102,6 +108,18 @@ def build_model(conf, weights, device):
     return model.to(device).eval()
 
 
+def apply_conv_half(model, on: bool):
+    """`--conv_half` of the sampling scripts: the conv UNets take it; a token model points at its own switch."""
+    if not on:
+        return
+    if hasattr(model, 'set_math'):
+        raise SystemExit(f'--conv_half is the conv UNets\' option; {type(model).__name__} is a token model: '
+                         f'use --math fp16 (scripts/sample_cfg.py) for its half-precision mode')
+    if not hasattr(model, 'set_conv_half'):
+        raise SystemExit(f'--conv_half: {type(model).__name__} has no native conv path')
+    model.set_conv_half(True)
+
+
 def parse_with_overrides(argv=None):
     args, unknown = get_parser().parse_known_args(argv)
     unknown = [(a[2:] if a.startswith('--') else a) for a in unknown]
@@ -145,6 +163,7 @@ def main(argv=None):
     torch.manual_seed(args.seed + env.rank)   # set_seed(seed, device_specific=True)
     diffuser = build_diffuser(args, conf, env.device)
     model = build_model(conf, args.weights, env.device)
+    apply_conv_half(model, args.conv_half)
     os.makedirs(args.save_dir, exist_ok=True)
     img_shape = (conf.data.img_channels, conf.data.params.img_size, conf.data.params.img_size)
     bspp = per_process_batch(args.n_samples, args.batch_size, env.world)

@@ -137,6 +137,28 @@ int dm_unet_plan_stats(const dm_unet* m, int64_t* builds, int* cached);
  * shape and arithmetic). get reports the caller's kind. */
 int dm_unet_set_conv_math(dm_unet* m, int kind);
 int dm_unet_get_conv_math(const dm_unet* m, int* kind);
+/* Conv-half option (opt-in, off by default; not an fp32-parity mode): an on/off switch of the handle
+ * beside its arithmetic, not a fourth kind of it -- dm_unet_set_conv_math keeps refusing DM_MATH_FP16, which stays the
+ * token models' mode. With the switch on, a plan of the DM_SPLIT_FP16X2 arithmetic runs its covered 3x3 convs with ONE
+ * matrix-core product per MAC (fp16x2 spends three, its Winograd form two); fp32 and bf16x3 plans, the range
+ * fallback's included, are unchanged, and so is everything with the switch off.
+ *   Covered: taps 9, stride 1, no upsample, Cin % 32 == 0 (both segments), Cout % 32 == 0, a map of >= 64 pixels whose
+ *   width is 8, 16 or 32 or a multiple of 32 from 64 to 256.
+ *   Operands: a' = fp16_rne(prologue(x)) -- the GroupNorm affine, with or without SiLU, in fp32 as the fp16x2 kernels
+ *   evaluate it; unscaled, bit for bit the high piece of their split -- and for a ResBlock's 1x1 shortcut segment
+ *   a2' = fp16_rne(x2); w' = the high piece of the fp16x2 weight image (its per-output-channel power-of-two scale
+ *   included, read in place: no weight copy). acc = sum_k a' w' over both segments in the fp32 accumulator of
+ *   v_mfma_f32_16x16x32_f16, times the exact inverse row scale, then the fp32 epilogue (bias, per-image row vector,
+ *   residual). The two image planes are plan workspace (dm_unet_memory reports them).
+ *   Range guard: |prologue(x)| or |x2| > 65504 raises the fp16x2 range flag; that forward is re-run in bf16x3, counted
+ *   once, and the next one is conv-half again. Deferred mode and the poll work as for fp16x2.
+ *   Not covered (exactly as in fp16x2): the first and last conv, stride-2, nearest-upsample / sub-pixel and 1x1 convs,
+ *   every attention kernel, 4x4 and smaller maps, GroupNorm statistics and tables, the time / class embedding path,
+ *   the resampling passes and the sampler step. There is no fp16 Winograd form. A covered conv the kernel refuses
+ *   runs as in fp16x2.
+ * Setting a different value drops the cached plans. */
+int dm_unet_set_conv_half(dm_unet* m, int on);
+int dm_unet_get_conv_half(const dm_unet* m, int* on);
 /* Deferred range check: with deferred != 0 a forward does not read the fp16x2 range flag (no host
  * sync per forward); the caller polls it once per sampling loop. dm_unet_range_poll synchronises
  * `stream`, reports whether any forward since the last poll met an activation beyond the fp16 range,
