@@ -40,6 +40,7 @@ void refresh_toggles() {
   t.range_check = !env_is("DM_RANGE_CHECK", '0');
   t.graph = std::getenv("DM_NO_GRAPH") == nullptr;
   t.wino = !env_is("DM_CONV_WINO", '0');
+  t.subwino = !env_is("DM_CONV_SUBWINO", '0');
   t.k32s_w4 = env_is("DM_K32S_W4", '1');
   t.k32_small = !env_is("DM_CONV_K32S", '0');
   t.k32_s2 = !env_is("DM_CONV_K32S2", '0');
@@ -265,9 +266,14 @@ static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part
       dm::set_error("conv: w_wino needs w_split of kind DM_SPLIT_FP16X2");
       return DM_ERR_ARG;
     }
-    a.wino_ws = d->w_wino;
-    a.wino_rowscale = dm::wino_rowscale(d->w_wino, a.Cout, a.Cin1, a.Cin2);
-    a.wino_fold = d->w_wino_fold;
+    if (a.upsample == 2) {  // the sub-pixel form: w_wino is dm_pack_conv_weight_subwino's image
+      a.subwino_ws = d->w_wino;
+      a.subwino_rowscale = dm::subwino_rowscale(d->w_wino, a.Cout, a.Cin1);
+    } else {
+      a.wino_ws = d->w_wino;
+      a.wino_rowscale = dm::wino_rowscale(d->w_wino, a.Cout, a.Cin1, a.Cin2);
+      a.wino_fold = d->w_wino_fold;
+    }
   }
   if (gin) {
     if (a.pro_scale || !gin->part || gin->G <= 0 || a.Cin1 <= 0 || a.Cin1 % gin->G != 0 || gin->nchunk <= 0 ||
@@ -335,6 +341,15 @@ extern "C" int64_t dm_conv_weight_wino_bytes(int Cout, int Cin, int Cin2) {
 
 extern "C" int dm_pack_conv_weight_wino(const float* w, int Cout, int Cin, int Cin2, int fold, void* out, void* stream) {
   return dm::wino_weights(w, Cout, Cin, Cin2, fold, out, (hipStream_t)stream);
+}
+
+extern "C" int64_t dm_conv_weight_subwino_bytes(int Cout, int Cin) {
+  if (Cout <= 0 || Cin <= 0 || Cin % 32 != 0) return -1;
+  return (int64_t)dm::subwino_weights_bytes(Cout, Cin);
+}
+
+extern "C" int dm_pack_conv_weight_subwino(const float* w, int Cout, int Cin, void* out, void* stream) {
+  return dm::subwino_weights(w, Cout, Cin, out, (hipStream_t)stream);
 }
 
 extern "C" int64_t dm_conv_weight_split_bytes(int nmat, int Cout, int K, int kind) {

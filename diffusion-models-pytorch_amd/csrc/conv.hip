@@ -285,7 +285,11 @@ int conv2d_igemm(const ConvArgs& a, hipStream_t st) {
   const long M = (long)a.B * a.Hout * a.Wout;
   DM_REQUIRE(M > 0 && M < (1L << 31), "conv: M out of range");
   if (a.h16) return conv2d_h16(a, st);  // a conv the plan marked for the conv-half kernel (conv_h16.hip)
-  DM_REQUIRE(a.tile >= 0 && a.tile <= 22, "conv: tile must be 0..22");
+  DM_REQUIRE(a.tile >= 0 && a.tile <= 23, "conv: tile must be 0..23");
+  if (a.tile == 23 || (a.tile == 0 && a.subwino_ws)) {  // the sub-pixel Winograd upsample kernel (conv_subwino.hip)
+    if (conv_subwino_ok(a)) return conv2d_subwino(a, st);
+    DM_REQUIRE(a.tile == 0, "conv: tile 23 needs sub-pixel Winograd weights and a shape conv_subwino_kernel takes");
+  }
   if (a.tile == 21 || (a.tile == 0 && a.wino_ws)) {  // the Winograd F(2,3) kernel (conv_wino.hip)
     if (conv_wino_ok(a)) {
       if (!a.gn_part || conv_can_emit_gn(a)) return conv2d_wino(a, st);
@@ -340,6 +344,7 @@ int conv_pick(const ConvArgs& a) {
   if (a.tile == 19 && conv_k32_variant_ok(a, 10)) return 3;  // forced K32 2-D tiles of wide maps
   if (a.tile == 20 && conv_k32_variant_ok(a, 11)) return 3;  // forced K32 64-row single-image tiles (8^2)
   if (a.tile == 22 && conv_k32_variant_ok(a, 13)) return 5;  // forced K32 stride-2 row-segment tiles (Wout > 64)
+  if (a.tile == 23 && conv_subwino_ok(a)) return 3;  // forced sub-pixel Winograd upsample kernel (conv_subwino.hip)
   if (conv_pw_ok(a)) {  // split 1x1: 128x128 tiles when they still give >= 2 blocks per CU, else 128x64
     const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
     return (a.Cout >= 128 && ((M + 127) / 128) * ((a.Cout + 127) / 128) >= 512) ? 3 : 4;
@@ -364,6 +369,7 @@ bool conv_can_emit_gn(const ConvArgs& a) {
   if (a.ksplit > 1)
     return !a.upsample && a.Hout * a.Wout <= kGnPixPerChunk && a.gn_G > 0 && a.Cout % a.gn_G == 0 &&
            a.Cout <= 1024;
+  if ((a.tile == 0 || a.tile == 23) && conv_subwino_ok(a)) return true;  // (conv_subwino_shape_ok's group rule)
   if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a))  // StagedEpilogue over 64-pixel chunks of one image
     return a.gn_G > 0 && a.Cout % a.gn_G == 0 && (a.Cout / a.gn_G) % 4 == 0 && a.Cout / a.gn_G <= 32;
   // the K32 stride-2 tiles: a block's 64 rows are one 64-pixel chunk (two 32-row waves per column slice)
@@ -399,6 +405,7 @@ std::string conv_label(const ConvArgs& a) {
                                 "conv_patch_kernel<256,256,128,128", "conv_patch_kernel<512,128,128,128",
                                 "conv_patch_kernel<128,128,64,64"};
   if (a.h16) return conv_h16_label(a);
+  if ((a.tile == 0 || a.tile == 23) && conv_subwino_ok(a)) return conv_subwino_label(a);
   if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a)) return conv_wino_label(a);
   if (const int k32 = a.k32_resolved ? a.k32_resolved - 1 : conv_k32_pick(a)) return conv_k32_label(a, k32);
   const int p = conv_pick(a);

@@ -18,6 +18,8 @@ struct Toggles {
   bool range_check = true;    // DM_RANGE_CHECK=0: no per-forward range flag check (and no fp32 re-run)
   bool graph = true;          // DM_NO_GRAPH: launch the plan op by op instead of as a hipGraph
   bool wino = true;           // DM_CONV_WINO=0: the 3x3 convs of 32^2 / 16^2 maps on conv_k32 instead of conv_wino
+  bool subwino = true;        // DM_CONV_SUBWINO=0: the Upsample convs of 4^2 / 8^2 / 16-wide low-res maps as four
+                              // sub-pixel convs (conv_k32, conv_patch3 MODE 2) instead of conv_subwino
   bool k32s_w4 = false;       // DM_K32S_W4=1: the small-map conv's 4-wave form (conv_k32 variant 12)
   bool k32_small = true;      // DM_CONV_K32S=0: split-K convs of <= 16-pixel maps as two launches (conv_k32 3 / 4)
   bool k32_s2 = true;         // DM_CONV_K32S2=0: stride-2 convs on conv_patch3 MODE 4 instead of conv_k32 variant 9
@@ -146,6 +148,11 @@ struct ConvArgs {
   int h16;
   const _Float16* h16_a1;
   const _Float16* h16_a2;
+  // optional sub-pixel Winograd weights of an upsample conv in its sub-pixel form (upsample = 2; conv_subwino.hip,
+  // subwino_weights): fp16x2 fragment images of the six U matrices [Cout][2 Cin1] with their inverse row scales; set,
+  // the shapes conv_subwino_ok takes run conv_subwino_kernel, every other the sub-pixel conv of `w` / `ws` as before
+  const void* subwino_ws;
+  const float* subwino_rowscale;
 };
 
 // Patch-pixel capacity of the halo-patch kernels' LDS images (fp32 / split-bf16; 128- / 64-row tiles)
@@ -355,6 +362,18 @@ const float* wino_rowscale(const void* ws, int Cout, int Cin1, int Cin2);
 int wino_weights(const float* w, int Cout, int Cin1, int Cin2, int fold, void* out, hipStream_t st);
 std::string conv_wino_label(const ConvArgs& a);
 int conv2d_wino(const ConvArgs& a, hipStream_t st);
+// Sub-pixel Winograd upsample convs (conv_subwino.hip): the sub-pixel form (upsample = 2) of a nearest-2x + 3x3 conv
+// on 16-wide (rows % 4 == 0), 8 x 8 and 4 x 4 low-res maps, Cin % 32 == 0, Cout % 128 == 0, bias-only epilogue, no
+// prologue. subwino_pack: the six U matrices [6][Cout][2 Cin] in fp32 from the torch weight [Cout][Cin][3][3]
+// (float64 sums, one rounding); subwino_weights: that and their fp16x2 split (split_conv_weights, nmat 6, ntap 2).
+bool conv_subwino_shape_ok(const ConvArgs& a);
+bool conv_subwino_ok(const ConvArgs& a);
+size_t subwino_weights_bytes(int Cout, int Cin);
+const float* subwino_rowscale(const void* ws, int Cout, int Cin);
+int subwino_pack(const float* w, int Cout, int Cin, float* out, hipStream_t st);
+int subwino_weights(const float* w, int Cout, int Cin, void* out, hipStream_t st);
+std::string conv_subwino_label(const ConvArgs& a);
+int conv2d_subwino(const ConvArgs& a, hipStream_t st);
 // static-weight GEMM on pre-split weights with K = 32 MFMA steps (linear_k32.hip)
 bool linear_k32_ok(const GemmArgs& g);
 int linear_k32(const GemmArgs& g, hipStream_t st);

@@ -49,6 +49,7 @@ struct ExecNet {
   // weights, shortcut fold), made at the first plan build that wants them
   std::map<std::pair<const float*, int>, void*> split_w;
   std::map<std::pair<const float*, int>, void*> wino_w;
+  std::map<const float*, void*> subwino_w;  // sub-pixel Winograd images per packed U matrices (subwino_for)
   size_t split_bytes = 0;
   std::map<const float*, int> w_exp;  // fp16x2 GEMMs: the weights' operand exponents (split_gemm)
   // the UNet plans put the Winograd kernel on 4 x 4 maps (a split-K form, where maybe_split chose wino_small_ks
@@ -67,6 +68,7 @@ struct ExecNet {
   ~ExecNet() {
     for (auto& kv : split_w) (void)hipFree(kv.second);
     for (auto& kv : wino_w) (void)hipFree(kv.second);
+    for (auto& kv : subwino_w) (void)hipFree(kv.second);
     if (range_flag) (void)hipFree(range_flag);
     if (range_flag_host) (void)hipHostFree(range_flag_host);
     if (arena) (void)hipFree(arena);
@@ -177,6 +179,35 @@ struct ExecNet {
     c.wino_ws = wp;
     c.wino_rowscale = wino_rowscale(wp, c.Cout, c.Cin1, c.Cin2);
     c.wino_fold = fold;
+  }
+
+  // Attach the sub-pixel Winograd weights (conv_subwino.hip) to an upsample conv in its sub-pixel form that split_for
+  // gave its fp16x2 copy: u = the packed U matrices [6][Cout][2 Cin] (Packer::subwino), split on first use.
+  // DM_CONV_SUBWINO=0, another arithmetic, a conv-half conv or a shape the kernel does not take: the conv stays as it is.
+  void subwino_for(ConvArgs& c, const float* u) {
+    c.subwino_ws = nullptr;
+    c.subwino_rowscale = nullptr;
+    if (!u || conv_math != 2 || !toggles().subwino || c.ws_np != 2 || !c.ws || c.h16 || !conv_subwino_shape_ok(c)) return;
+    auto it = subwino_w.find(u);
+    void* wp = nullptr;
+    if (it != subwino_w.end()) {
+      wp = it->second;
+    } else {
+      const size_t nb = subwino_weights_bytes(c.Cout, c.Cin1);
+      if (hipMalloc(&wp, nb) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+      }
+      if (split_conv_weights(u, 6, c.Cout, 2 * c.Cin1, c.Cin1, 2, 2, wp, nullptr) != DM_OK ||
+          hipDeviceSynchronize() != hipSuccess) {
+        (void)hipFree(wp);
+        return;
+      }
+      subwino_w[u] = wp;
+      split_bytes += nb;
+    }
+    c.subwino_ws = wp;
+    c.subwino_rowscale = subwino_rowscale(wp, c.Cout, c.Cin1);
   }
 
   // fp16x2 GEMMs (gemm.hip SPLIT): A scaled by 2^ea, B by the weight's exponent (max |w| * 2^eb in [2^13, 2^14);

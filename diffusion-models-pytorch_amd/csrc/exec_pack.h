@@ -29,7 +29,7 @@ struct ParamReader {
 
 // A copy / repack job into the weight arena.
 struct PackJob {
-  int kind;  // 0 raw copy, 1 conv repack, 2 add (bias sum), 3 sub-pixel upsample repack
+  int kind;  // 0 raw copy, 1 conv repack, 2 add (bias sum), 3 sub-pixel upsample repack, 4 sub-pixel Winograd U matrices
   const float* src;
   const float* src2;
   int64_t n;
@@ -62,6 +62,12 @@ struct Packer {
     jobs.push_back({3, w, nullptr, (int64_t)Cout * Cin * 9, Cout, Cin, 9, 0, 0, off});
     return off;
   }
+  // the six U matrices [6][Cout][2 Cin] of the sub-pixel Winograd upsample kernel (conv_subwino.hip), from the torch weight
+  size_t subwino(const float* w, int Cout, int Cin) {
+    const size_t off = reserve((int64_t)12 * Cout * Cin);
+    jobs.push_back({4, w, nullptr, (int64_t)Cout * Cin * 9, Cout, Cin, 9, 0, 0, off});
+    return off;
+  }
 };
 
 static __global__ void vec_add_kernel(const float* a, const float* b, float* out, int64_t n) {
@@ -83,6 +89,9 @@ inline int run_pack_jobs(const Packer& pk, float* arena, hipStream_t st) {
       if (rc) return rc;
     } else if (j.kind == 3) {
       const int rc = repack_subpixel(j.src, j.Cout, j.Cin, arena + j.dst, st);
+      if (rc) return rc;
+    } else if (j.kind == 4) {
+      const int rc = subwino_pack(j.src, j.Cout, j.Cin, arena + j.dst, st);
       if (rc) return rc;
     } else {
       hipLaunchKernelGGL(vec_add_kernel, dim3((unsigned)((j.n + 255) / 256)), dim3(256), 0, st, j.src, j.src2,

@@ -35,6 +35,8 @@ struct ConvP {
   size_t w, bias;
   int Cout, Cin, taps, K;
   size_t w_sub = 0;  // sub-pixel weights [4][Cout][4 Cin] of an upsample conv (0 = none)
+  size_t w_subw = 0;  // sub-pixel Winograd U matrices [6][Cout][2 Cin] of an Upsample conv (0 = none)
+  bool has_subw = false;
 };
 
 struct ResBlockP {
@@ -474,7 +476,13 @@ static int unet_create(const dm_unet_arch* arch, const float* const* params, con
     c.w = pk.reserve((int64_t)C * 9 * C);
     pk.conv_at(w, C, C, 9, 9 * C, 0, c.w);
     c.bias = pk.raw(b, C);
-    if (std::string(what) == "Upsample") c.w_sub = pk.subpix(w, C, C);
+    if (std::string(what) == "Upsample") {
+      c.w_sub = pk.subpix(w, C, C);
+      if (C % 128 == 0) {  // (the channel counts conv_subwino takes)
+        c.w_subw = pk.subwino(w, C, C);
+        c.has_subw = true;
+      }
+    }
     m->convs.push_back(c);
     return (int)m->convs.size() - 1;
   };
@@ -1262,6 +1270,8 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         s.upsample = 2; s.w = P(cv.w_sub); s.K = 4 * c.Cin1;
         split_for(s);
         if (conv_pick(s) >= 3) c = s;
+        // whole-row low-res maps of 4 / 8 / 16 columns: the sub-pixel Winograd kernel (3/4 of the MFMA products)
+        if (c.upsample == 2 && cv.has_subw) subwino_for(c, P(cv.w_subw));
       }
       if (c.upsample == 2) {
         emit_conv(c, y);  // the K32 sub-pixel conv's epilogue emits the consumer's GroupNorm partials

@@ -280,6 +280,10 @@ def _declare(L: ctypes.CDLL):
     L.dm_conv_weight_wino_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.dm_conv_weight_wino_bytes.restype = ctypes.c_int64
     L.dm_pack_conv_weight_wino.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
+    if hasattr(L, 'dm_conv_weight_subwino_bytes'):   # (absent from an older build under DM_HIP_LIB: an A/B arm)
+        L.dm_conv_weight_subwino_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        L.dm_conv_weight_subwino_bytes.restype = ctypes.c_int64
+        L.dm_pack_conv_weight_subwino.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_conv_weight_split_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.dm_conv_weight_split_bytes.restype = ctypes.c_int64
     L.dm_pack_conv_weight_split.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -573,6 +577,21 @@ def pack_conv_weight_wino(wp: torch.Tensor, Cin: int, Cin2: int = 0, fold: bool 
     out = torch.empty(nbytes, dtype=torch.uint8, device=wp.device)
     check(load().dm_pack_conv_weight_wino(wp.data_ptr(), Cout, Cin, Cin2, int(bool(fold)), out.data_ptr(),
                                           stream_handle(wp.device)), 'dm_pack_conv_weight_wino')
+    return out
+
+
+def pack_conv_weight_subwino(w: torch.Tensor) -> torch.Tensor:
+    """torch 3x3 weight [Cout][Cin][3][3] of a nearest-2x + 3x3 upsample conv -> the sub-pixel Winograd weight images
+    (a uint8 device tensor) for ConvDesc.w_wino of the conv in its sub-pixel form (upsample = 2, with ConvDesc.w_split
+    of kind SPLIT_FP16X2 of the sub-pixel weights)."""
+    Cout, Cin, kh, kw = w.shape
+    nbytes = load().dm_conv_weight_subwino_bytes(Cout, Cin)
+    if nbytes <= 0 or (kh, kw) != (3, 3):
+        raise ValueError('sub-pixel Winograd packing needs a [Cout, Cin, 3, 3] weight, Cin % 32 == 0')
+    w = w.contiguous()
+    out = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    check(load().dm_pack_conv_weight_subwino(w.data_ptr(), Cout, Cin, out.data_ptr(), stream_handle(w.device)),
+          'dm_pack_conv_weight_subwino')
     return out
 
 

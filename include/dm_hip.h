@@ -521,6 +521,14 @@ int dm_pack_conv_weight_split(const float* w, int nmat, int Cout, int K, int Cin
 int64_t dm_conv_weight_wino_bytes(int Cout, int Cin, int Cin2);
 int dm_pack_conv_weight_wino(const float* w, int Cout, int Cin, int Cin2, int fold, void* out, void* stream);
 
+/* Sub-pixel Winograd weights of a nearest-2x + 3x3 upsample conv, from the torch weight w [Cout][Cin][3][3]
+ * (Cin % 32 == 0): along x the three F(2,3) planes a nearest-upsampled row leaves (U = g0, g0 + g1 + g2, g2), along y
+ * the sub-pixel sums, six matrices [Cout][2 Cin] (float64, one rounding), split to fp16x2 fragment images with
+ * per-output-channel power-of-two scales: dm_conv_weight_subwino_bytes(Cout, Cin) bytes at `out`. Passed as
+ * dm_conv_desc.w_wino of a conv in the sub-pixel form (upsample = 2). */
+int64_t dm_conv_weight_subwino_bytes(int Cout, int Cin);
+int dm_pack_conv_weight_subwino(const float* w, int Cout, int Cin, void* out, void* stream);
+
 typedef struct dm_conv_desc {
   const float* x;  int x_pitch, Cin, Hin, Win;
   int taps, stride;
@@ -551,7 +559,10 @@ typedef struct dm_conv_desc {
   float* kpart;
   /* optional Winograd F(2,3) weights of a 3x3 stride-1 conv from dm_pack_conv_weight_wino (needs w_split of kind
    * DM_SPLIT_FP16X2 too): 32- / 16-pixel-wide maps with Cout % 128 == 0 then run the Winograd kernel (tile 0 or
-   * 21; 21 fails on any other shape) */
+   * 21; 21 fails on any other shape). With upsample = 2: the sub-pixel Winograd weights from
+   * dm_pack_conv_weight_subwino instead (w_split of kind DM_SPLIT_FP16X2 of the sub-pixel weights too): 16-wide,
+   * 8 x 8 and 4 x 4 low-res maps with Cout % 128 == 0 and a bias-only epilogue then run the sub-pixel Winograd
+   * kernel (tile 0 or 23; 23 fails on any other shape), w_wino_fold unused */
   const void* w_wino;
   int w_wino_fold;   /* the fold dm_pack_conv_weight_wino packed w_wino with */
 } dm_conv_desc;

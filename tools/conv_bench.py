@@ -85,6 +85,9 @@ def run(name, iters, split, tile=0, ksplit=0):
     if tile == 21:  # the Winograd F(2,3) kernel (conv_wino.hip)
         ww = dmhip.pack_conv_weight_wino(wp, Cin)
         d.w_wino = ww.data_ptr()  # (no shortcut segment here: the fold does not apply)
+    if tile == 23:  # the sub-pixel Winograd upsample kernel (conv_subwino.hip), from the torch weight
+        ww = dmhip.pack_conv_weight_subwino(w)
+        d.w_wino = ww.data_ptr()
     if ksplit > 1:
         kpart = torch.empty((ksplit, B * Ho * Ho, Cout), device=dev)
         d.ksplit, d.kpart = ksplit, kpart.data_ptr()
