@@ -229,11 +229,12 @@ struct GinHook {
   const float *gamma, *beta, *ms, *mb;
   int mp;
 };
-static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, void* stream,
-                            const GinHook* gin = nullptr) {
+// the ConvArgs of a descriptor (no HIP call, no tensor read: dm_debug_conv_choice builds its ConvArgs here too)
+static int conv_args_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, const GinHook* gin,
+                               dm::ConvArgs& a) {
   dm::refresh_toggles();
   if (!d || !d->x || !d->w || !d->y) { dm::set_error("null tensor"); return DM_ERR_ARG; }
-  dm::ConvArgs a{};
+  a = dm::ConvArgs{};
   a.s2_pad0 = s2_pad0;
   a.gn_part = gn_part;
   a.gn_G = gn_G;
@@ -288,16 +289,23 @@ static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part
     a.gin_n = (double)a.Hin * a.Win * (a.Cin1 / gin->G);
     a.gin_eps = gin->eps; a.gin_gamma = gin->gamma; a.gin_beta = gin->beta;
     a.gin_ms = gin->ms; a.gin_mb = gin->mb; a.gin_mp = gin->mp;
-    if (!dm::conv_lds_tables(a)) {
-      dm::set_error("dm_debug_conv2d_gin: the conv does not stage its GroupNorm tables in LDS (conv_lds_tables)");
+    if (!dm::conv_choose(a).lds_tables) {
+      dm::set_error("dm_debug_conv2d_gin: the conv does not stage its GroupNorm tables in LDS (ConvChoice::lds_tables)");
       return DM_ERR_UNSUPPORTED;
     }
   }
-  const int rc = dm::conv2d_igemm(a, (hipStream_t)stream);
-  // dm_debug_conv2d_gn / dm_debug_conv2d_gin (null on every other entry) and dm_debug_launch_log(2): conv_label(a) goes to the launch log after the
-  // launchers' own lines. It is the dispatcher's choice restated from the same ConvArgs (the label function the
-  // profiles use, which mirrors conv2d_igemm's dispatch), not a record made by the launcher.
-  if ((gn_part || gin || dm::g_launch_log_convs) && rc == DM_OK) dm::note_launch(dm::conv_label(a).c_str());
+  return DM_OK;
+}
+
+static int conv2d_from_desc(const dm_conv_desc* d, int s2_pad0, double2* gn_part, int gn_G, void* stream,
+                            const GinHook* gin = nullptr) {
+  dm::ConvArgs a;
+  if (const int rc0 = conv_args_from_desc(d, s2_pad0, gn_part, gn_G, gin, a)) return rc0;
+  const dm::ConvChoice ch = dm::conv_choose(a);
+  const int rc = dm::conv2d_run(a, ch, (hipStream_t)stream);
+  // dm_debug_conv2d_gn / dm_debug_conv2d_gin (null on every other entry) and dm_debug_launch_log(2): the label of the
+  // choice that was launched goes to the launch log after the launchers' own lines
+  if ((gn_part || gin || dm::g_launch_log_convs) && rc == DM_OK) dm::note_launch(dm::conv_label(a, ch).c_str());
   return rc;
 }
 
@@ -322,7 +330,7 @@ extern "C" int dm_debug_conv2d_gn(const dm_conv_desc* d, int s2_pad0, int G, voi
 
 // Operator tests of the convs' in-kernel GroupNorm finalize (tests/test_gpu_norm_ops.py): the conv of `d` (pro_scale
 // null, pro_nosilu honoured) with its prologue tables built in the kernel from the chunk partials gin_part
-// [B][gin_nchunk][gin_G] of x, gin_n = Hin Win Cin / gin_G. DM_ERR_UNSUPPORTED where conv_lds_tables() is false;
+// [B][gin_nchunk][gin_G] of x, gin_n = Hin Win Cin / gin_G. DM_ERR_UNSUPPORTED where ConvChoice::lds_tables is false;
 // gin_ms and gin_mb come together or not at all (the plans' AdaGN form).
 extern "C" int dm_debug_conv2d_gin(const dm_conv_desc* d, int s2_pad0, const void* gin_part, int gin_G, int gin_nchunk,
                                    float gin_eps, const float* gin_gamma, const float* gin_beta, const float* gin_ms,
@@ -332,6 +340,53 @@ extern "C" int dm_debug_conv2d_gin(const dm_conv_desc* d, int s2_pad0, const voi
   const int rc = conv2d_from_desc(d, s2_pad0, nullptr, 0, stream, &gin);
   if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == DM_OK) { dm::set_error("sync"); return DM_ERR_HIP; }
   return rc;
+}
+
+// Host-only window onto the conv dispatch (tests/test_conv_dispatch_host.py): which kernel the conv of `d` would run,
+// without a HIP call or a tensor read. The ConvArgs are conv2d_from_desc's, plus what the plans set beside a
+// descriptor: pick_B, a split-K workspace (ksplit_has_part: a stand-in address where d->kpart is null), the conv-half
+// mark with stand-in planes (h16), statistics requested from the epilogue (gn_emit: gn_part set, GroupNorm(gn_G)) and
+// the in-kernel GroupNorm finalize (gin_G > 0). Everything reported is conv_choose's: label, launched ("family:variant",
+// or "refused"), lds_tables; emits_gn from the choice of the same conv with gn_part set, as the plans ask (0 where
+// gn_G <= 0).
+extern "C" int dm_debug_conv_choice(const dm_conv_desc* d, int s2_pad0, int gn_G, int gn_emit, int pick_B,
+                                    int ksplit_has_part, int h16, int gin_G, int gin_nchunk, char* label, int label_len,
+                                    int* emits_gn, int* lds_tables, char* launched, int launched_len) {
+  if (!d || !label || label_len <= 0 || !emits_gn || !lds_tables || !launched || launched_len <= 0) {
+    dm::set_error("dm_debug_conv_choice: arguments");
+    return DM_ERR_ARG;
+  }
+  auto put = [](char* dst, int len, const std::string& s) {
+    const size_t n = std::min(s.size(), (size_t)len - 1);
+    memcpy(dst, s.data(), n);
+    dst[n] = 0;
+  };
+  put(label, label_len, "");
+  put(launched, launched_len, "refused");
+  *emits_gn = *lds_tables = 0;
+  double2* const standin = reinterpret_cast<double2*>(uintptr_t(1) << 20);  // never read
+  const GinHook gin{standin, gin_G, gin_nchunk, 1e-5f, reinterpret_cast<const float*>(standin),
+                    reinterpret_cast<const float*>(standin), nullptr, nullptr, 0};
+  dm::ConvArgs a;
+  if (conv_args_from_desc(d, s2_pad0, gn_emit ? standin : nullptr, gn_G, gin_G > 0 ? &gin : nullptr, a)) return DM_OK;
+  a.pick_B = pick_B;
+  if (ksplit_has_part && !a.kpart) a.kpart = reinterpret_cast<float*>(standin);
+  if (h16) {
+    a.h16 = 1;
+    a.h16_a1 = reinterpret_cast<const _Float16*>(standin);
+    if (a.Cin2 > 0) a.h16_a2 = reinterpret_cast<const _Float16*>(standin);
+  }
+  const dm::ConvChoice ch = dm::conv_choose(a);
+  if (ch.error) return DM_OK;
+  put(launched, launched_len, dm::conv_choice_name(a, ch));
+  put(label, label_len, dm::conv_label(a, ch));
+  if (gn_G > 0) {
+    dm::ConvArgs e = a;
+    e.gn_part = standin;
+    *emits_gn = dm::conv_choose(e).emits_gn ? 1 : 0;
+  }
+  *lds_tables = ch.lds_tables ? 1 : 0;
+  return DM_OK;
 }
 
 extern "C" int64_t dm_conv_weight_wino_bytes(int Cout, int Cin, int Cin2) {

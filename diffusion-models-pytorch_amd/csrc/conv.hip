@@ -254,179 +254,284 @@ inline int conv_mode(const ConvArgs& a) {
   return a.stride == 2 ? CM_3X3_S2 : CM_3X3_S1;
 }
 
-}  // namespace
+// The public forcing knob (dm_conv_desc.tile, ConvArgs::tile) -> the kernel form it names: the only place the numbers
+// mean anything (DESIGN.md §4.21 has the table in words). 0 is the automatic choice. A forced form that does not fit
+// falls back to Im2col (the halo-patch tiles 4..6 to their own shape, every other to 128 x 128), except 21 and 23,
+// which are errors then. (A conv marked h16 reads tile as conv_h16_form does: 1 / 2 force H16Form::Rows / T2D.)
+struct TileForm {
+  ConvFamily family;
+  ConvTile tile;
+  K32Form k32;
+};
+constexpr TileForm tiled(ConvFamily f, ConvTile t) { return {f, t, K32Form::None}; }
+constexpr TileForm k32_form(K32Form k) {
+  return {k == K32Form::Small8 ? ConvFamily::K32Small : ConvFamily::K32, ConvTile::None, k};
+}
+constexpr int kNumTiles = 24;
+const TileForm kTileForms[kNumTiles] = {
+    /* 0 */ tiled(ConvFamily::Im2col, ConvTile::None),  // automatic
+    /* 1 */ tiled(ConvFamily::Im2col, ConvTile::T128x128),
+    /* 2 */ tiled(ConvFamily::Im2col, ConvTile::T128x64),
+    /* 3 */ tiled(ConvFamily::Im2col, ConvTile::T64x64),
+    /* 4 */ tiled(ConvFamily::Patch, ConvTile::T128x128),  // 4..6: fp32 (Patch) or split (Patch3) by the conv's weights
+    /* 5 */ tiled(ConvFamily::Patch, ConvTile::T128x64),
+    /* 6 */ tiled(ConvFamily::Patch, ConvTile::T64x64),
+    /* 7 */ tiled(ConvFamily::Patch3, ConvTile::T256x256),  // 7..9: fp16x2 only
+    /* 8 */ tiled(ConvFamily::Patch3, ConvTile::T512x128),
+    /* 9 */ tiled(ConvFamily::Patch3, ConvTile::Seg128),
+    /* 10 */ k32_form(K32Form::T128x128),
+    /* 11 */ k32_form(K32Form::T128x64),
+    /* 12 */ k32_form(K32Form::SplitK64x64),
+    /* 13 */ k32_form(K32Form::SplitK64x128),
+    /* 14 */ k32_form(K32Form::Seg64),
+    /* 15 */ k32_form(K32Form::Small8),
+    /* 16 */ k32_form(K32Form::Wide512),
+    /* 17 */ k32_form(K32Form::BigTab),
+    /* 18 */ k32_form(K32Form::S2),
+    /* 19 */ k32_form(K32Form::T2D),
+    /* 20 */ k32_form(K32Form::Rows64),
+    /* 21 */ tiled(ConvFamily::Wino, ConvTile::None),
+    /* 22 */ k32_form(K32Form::S2Seg),
+    /* 23 */ tiled(ConvFamily::SubWino, ConvTile::None),
+};
 
-int conv2d_igemm(const ConvArgs& a, hipStream_t st) {
-  DM_REQUIRE(a.taps == 1 || a.taps == 9, "conv: taps must be 1 or 9");
-  DM_REQUIRE(a.stride == 1 || a.stride == 2, "conv: stride must be 1 or 2");
-  DM_REQUIRE(!a.upsample || (a.taps == 9 && a.stride == 1), "conv: upsample needs 3x3 stride 1");
-  DM_REQUIRE(a.upsample >= 0 && a.upsample <= 2, "conv: upsample must be 0, 1 (nearest) or 2 (sub-pixel)");
-  DM_REQUIRE(a.Cin1 % kBK == 0 && a.Cin2 % kBK == 0, "conv: input channels must be multiples of 32");
-  DM_REQUIRE(a.Cin1 + kBK <= kZeroPageFloats, "conv: too many input channels for the zero-padding page");
-  DM_REQUIRE(a.Cin1 > 0, "conv: no input channels");
-  DM_REQUIRE(a.K == (a.upsample == 2 ? 4 : a.taps) * a.Cin1 + a.Cin2, "conv: K mismatch");
-  DM_REQUIRE(a.upsample != 2 || a.Cin2 == 0, "conv: sub-pixel upsample has no second segment");
-  DM_REQUIRE(a.x1_pitch % 4 == 0 && a.y_pitch >= a.Cout && a.K % 4 == 0, "conv: pitch");
-  DM_REQUIRE(aligned16(a.x1) && aligned16(a.w), "conv: operands must be 16-byte aligned");
-  DM_REQUIRE(a.Cin2 == 0 || (a.x2 && aligned16(a.x2) && a.x2_pitch % 4 == 0), "conv: segment-2 operand");
-  DM_REQUIRE(a.Cout > 0 && a.B > 0 && a.Hin > 0 && a.Win > 0, "conv: empty problem");
+#define DM_REFUSE(cond, msg) \
+  do {                       \
+    if (!(cond)) return msg; \
+  } while (0)
+
+// a descriptor no kernel can be chosen for
+const char* conv_check_problem(const ConvArgs& a) {
+  DM_REFUSE(a.taps == 1 || a.taps == 9, "conv: taps must be 1 or 9");
+  DM_REFUSE(a.stride == 1 || a.stride == 2, "conv: stride must be 1 or 2");
+  DM_REFUSE(!a.upsample || (a.taps == 9 && a.stride == 1), "conv: upsample needs 3x3 stride 1");
+  DM_REFUSE(a.upsample >= 0 && a.upsample <= 2, "conv: upsample must be 0, 1 (nearest) or 2 (sub-pixel)");
+  DM_REFUSE(a.Cin1 % kBK == 0 && a.Cin2 % kBK == 0, "conv: input channels must be multiples of 32");
+  DM_REFUSE(a.Cin1 + kBK <= kZeroPageFloats, "conv: too many input channels for the zero-padding page");
+  DM_REFUSE(a.Cin1 > 0, "conv: no input channels");
+  DM_REFUSE(a.K == (a.upsample == 2 ? 4 : a.taps) * a.Cin1 + a.Cin2, "conv: K mismatch");
+  DM_REFUSE(a.upsample != 2 || a.Cin2 == 0, "conv: sub-pixel upsample has no second segment");
+  DM_REFUSE(a.Cout > 0 && a.B > 0 && a.Hin > 0 && a.Win > 0, "conv: empty problem");
   if (a.upsample) {
-    DM_REQUIRE(a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win, "conv: upsample output size");
+    DM_REFUSE(a.Hout == 2 * a.Hin && a.Wout == 2 * a.Win, "conv: upsample output size");
   } else if (a.s2_pad0) {  // input padded (0, 1, 0, 1): floor((H + 1 - 3) / 2) + 1 output rows
-    DM_REQUIRE(a.s2_pad0 == 1 && a.taps == 9 && a.stride == 2, "conv: s2_pad0 is for 3x3 stride-2 convs");
-    DM_REQUIRE(a.Hin >= 2 && a.Win >= 2 && a.Hout == (a.Hin - 2) / 2 + 1 && a.Wout == (a.Win - 2) / 2 + 1,
-               "conv: 3x3 stride-2 (bottom/right padding) output size");
+    DM_REFUSE(a.s2_pad0 == 1 && a.taps == 9 && a.stride == 2, "conv: s2_pad0 is for 3x3 stride-2 convs");
+    DM_REFUSE(a.Hin >= 2 && a.Win >= 2 && a.Hout == (a.Hin - 2) / 2 + 1 && a.Wout == (a.Win - 2) / 2 + 1,
+              "conv: 3x3 stride-2 (bottom/right padding) output size");
   } else if (a.taps == 9) {
-    DM_REQUIRE(a.Hout == (a.Hin - 1) / a.stride + 1 && a.Wout == (a.Win - 1) / a.stride + 1,
-               "conv: 3x3 output size");
+    DM_REFUSE(a.Hout == (a.Hin - 1) / a.stride + 1 && a.Wout == (a.Win - 1) / a.stride + 1, "conv: 3x3 output size");
   } else {
-    DM_REQUIRE(a.stride == 1 && a.Hout == a.Hin && a.Wout == a.Win, "conv: 1x1 output size");
+    DM_REFUSE(a.stride == 1 && a.Hout == a.Hin && a.Wout == a.Win, "conv: 1x1 output size");
   }
   const long M = (long)a.B * a.Hout * a.Wout;
-  DM_REQUIRE(M > 0 && M < (1L << 31), "conv: M out of range");
-  if (a.h16) return conv2d_h16(a, st);  // a conv the plan marked for the conv-half kernel (conv_h16.hip)
-  DM_REQUIRE(a.tile >= 0 && a.tile <= 23, "conv: tile must be 0..23");
-  if (a.tile == 23 || (a.tile == 0 && a.subwino_ws)) {  // the sub-pixel Winograd upsample kernel (conv_subwino.hip)
-    if (conv_subwino_ok(a)) return conv2d_subwino(a, st);
-    DM_REQUIRE(a.tile == 0, "conv: tile 23 needs sub-pixel Winograd weights and a shape conv_subwino_kernel takes");
+  DM_REFUSE(M > 0 && M < (1L << 31), "conv: M out of range");
+  return nullptr;
+}
+
+// operands every kernel refuses (a question asked before the buffers exist still gets its choice: ConvChoice::error)
+const char* conv_check_operands(const ConvArgs& a) {
+  DM_REFUSE(a.x1_pitch % 4 == 0 && a.y_pitch >= a.Cout && a.K % 4 == 0, "conv: pitch");
+  DM_REFUSE(aligned16(a.x1) && aligned16(a.w), "conv: operands must be 16-byte aligned");
+  DM_REFUSE(a.Cin2 == 0 || (a.x2 && aligned16(a.x2) && a.x2_pitch % 4 == 0), "conv: segment-2 operand");
+  return nullptr;
+}
+
+// the kernel, given the facts every family shares (conv_choose)
+const char* conv_choose_kernel(const ConvArgs& a, const TileForm& forced, bool automatic, bool pointwise, bool rows64,
+                               ConvTile halo, ConvChoice& ch) {
+  if (a.h16) {  // a conv the plan marked for the conv-half kernel
+    ch.family = ConvFamily::H16;
+    ch.h16 = conv_h16_form(a);
+    ch.emits_gn = conv_h16_can_emit(a);
+    DM_REFUSE(ch.h16 != H16Form::None && a.h16_a1 && (a.Cin2 == 0 || a.h16_a2),
+              "conv_h16: needs the fp16 image plane(s), fp16x2 split weights and a covered 3x3 stride-1 shape");
+    return nullptr;
   }
-  if (a.tile == 21 || (a.tile == 0 && a.wino_ws)) {  // the Winograd F(2,3) kernel (conv_wino.hip)
-    if (conv_wino_ok(a)) {
-      if (!a.gn_part || conv_can_emit_gn(a)) return conv2d_wino(a, st);
-      DM_REQUIRE(a.tile == 0, "conv: GroupNorm statistics need groups of 4..32 channels");
-      // (automatic choice) statistics the Winograd epilogue cannot emit: the direct kernels without its weights
-      ConvArgs d = a;
-      d.wino_ws = nullptr;
-      d.wino_rowscale = nullptr;
-      return conv2d_igemm(d, st);
+  DM_REFUSE(a.tile >= 0 && a.tile < kNumTiles, "conv: tile must be 0..23");
+  // the sub-pixel Winograd upsample kernel: forced, or the conv has its weights
+  if (forced.family == ConvFamily::SubWino || (automatic && a.subwino_ws)) {
+    if (conv_subwino_ok(a)) {
+      ch.family = ConvFamily::SubWino;
+      ch.emits_gn = true;  // (conv_subwino_shape_ok's group rule)
+      return nullptr;
     }
-    DM_REQUIRE(a.tile == 0, "conv: tile 21 needs Winograd weights and a shape conv_wino_kernel takes");
+    DM_REFUSE(automatic, "conv: tile 23 needs sub-pixel Winograd weights and a shape conv_subwino_kernel takes");
+  }
+  // the Winograd F(2,3) kernel, likewise
+  if (forced.family == ConvFamily::Wino || (automatic && a.wino_ws)) {
+    if (conv_wino_ok(a)) {
+      ch.emits_gn = a.ksplit > 1 ? conv_splitk_can_emit(a) : conv_wino_can_emit(a);
+      if (!a.gn_part || ch.emits_gn) {
+        ch.family = ConvFamily::Wino;
+        return nullptr;
+      }
+      DM_REFUSE(automatic, "conv: GroupNorm statistics need groups of 4..32 channels");
+      // (automatic choice) statistics the Winograd epilogue cannot emit: the direct kernels, below
+    } else {
+      DM_REFUSE(automatic, "conv: tile 21 needs Winograd weights and a shape conv_wino_kernel takes");
+    }
+  }
+  // the direct kernels. K32 where a form is forced and fits, or the automatic choice takes one
+  const bool force_k32 = forced.family == ConvFamily::K32 || forced.family == ConvFamily::K32Small;
+  ch.k32 = force_k32 ? (conv_k32_variant_ok(a, forced.k32) ? forced.k32 : K32Form::None)
+                     : automatic ? k32_choose(a, halo) : K32Form::None;
+  ch.emits_gn = a.ksplit > 1            ? conv_splitk_can_emit(a)
+                : ch.k32 != K32Form::None ? conv_k32_can_emit(a, ch.k32, rows64)
+                                          : rows64 && conv_patch_can_emit(a);
+  DM_REFUSE(!a.gn_part || ch.emits_gn, "conv: GroupNorm statistics need a 128-row halo-patch tile, whole 64-pixel "
+                                       "chunks and groups within 32 channels");
+  DM_REFUSE(!a.pro_scale || (ch.takes_prologue && a.pro_shift && aligned16(a.pro_scale) && aligned16(a.pro_shift)),
+            "conv: the GroupNorm prologue needs a halo-patch shape (3x3 stride 1 / upsample, whole-row tiles)");
+  if (ch.k32 != K32Form::None) {
+    ch.family = ch.k32 == K32Form::Small8 || ch.k32 == K32Form::Small4 ? ConvFamily::K32Small : ConvFamily::K32;
+    return nullptr;
+  }
+  const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
+  const long b128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
+  if (pointwise) {  // split 1x1: 128x128 tiles when they still give >= 2 blocks per CU, else 128x64
+    ch.family = ConvFamily::Pointwise3;
+    ch.tile = a.Cout >= 128 && b128 >= 512 ? ConvTile::T128x128 : ConvTile::T128x64;
+    return conv_patch3_refuses(a, ch);
+  }
+  if (halo != ConvTile::None) {
+    ch.tile = halo;
+    if (conv_patch3_ok(a, halo, ch.geom)) {
+      ch.family = ConvFamily::Patch3;
+      return conv_patch3_refuses(a, ch);
+    }
+    if (halo == ConvTile::T128x128 || halo == ConvTile::T128x64 || halo == ConvTile::T64x64) {
+      ch.family = ConvFamily::Patch;
+      return conv_patch_refuses(a);
+    }
+    ch.tile = ConvTile::T128x128;  // a split-only tile that does not fit: Im2col
+    return nullptr;
+  }
+  // Im2col: the forced tile, the im2col shape of a forced halo-patch tile that does not fit, 128 x 128 for any other
+  // forced form that does not; else the 128x128 tile when it still yields >= 2 waves of blocks over 256 CUs
+  DM_REFUSE(a.upsample != 2, "conv: the sub-pixel upsample runs on the halo-patch kernel only (shape has no "
+                             "whole-row tiling)");
+  if (!automatic) {
+    ch.tile = forced.family == ConvFamily::Im2col || forced.family == ConvFamily::Patch ? forced.tile : ConvTile::T128x128;
+    return nullptr;
+  }
+  const long b128x64 = ((M + 127) / 128) * ((a.Cout + 63) / 64);
+  ch.tile = a.Cout >= 128 && b128 >= 512 ? ConvTile::T128x128 : b128x64 >= 512 ? ConvTile::T128x64 : ConvTile::T64x64;
+  return nullptr;
+}
+
+#undef DM_REFUSE
+
+const char* tile_dims(ConvTile t) {
+  switch (t) {
+    case ConvTile::T128x64: return "128,64,64,32";
+    case ConvTile::T64x64: return "64,64,32,32";
+    case ConvTile::T256x256: return "256,256,128,128";
+    case ConvTile::T512x128: return "512,128,128,128";
+    default: return "128,128,64,64";  // T128x128, Seg128
+  }
+}
+
+}  // namespace
+
+// The one decision. First the facts every family shares -- the forced form, the conv's halo-patch tiling and what
+// the plans ask of it (takes_prologue, lds_tables: properties of that tiling, which the K32 and Winograd forms that
+// replace a halo-patch tile inherit) -- then the kernel, in the order of precedence H16, SubWino, Wino, K32,
+// Pointwise3, Patch3, Patch, Im2col.
+ConvChoice conv_choose(const ConvArgs& a) {
+  ConvChoice ch;
+  if ((ch.error = conv_check_problem(a))) return ch;
+  const bool automatic = a.tile == 0;
+  const TileForm forced = a.tile > 0 && a.tile < kNumTiles ? kTileForms[a.tile] : kTileForms[0];
+  const bool force_im2col = forced.family == ConvFamily::Im2col && forced.tile != ConvTile::None;
+  const bool force_halo = forced.family == ConvFamily::Patch || forced.family == ConvFamily::Patch3;
+  const bool pointwise = !force_im2col && conv_pw_ok(a);
+  ConvTile halo = ConvTile::None;
+  if (automatic || force_halo) halo = conv_patch_pick(a, forced.tile, ch.geom);
+  if (halo == ConvTile::None) ch.geom = PatchGeom{};
+  // another family's forced form that fits takes the prologue too
+  const bool force_k32 = forced.family == ConvFamily::K32 || forced.family == ConvFamily::K32Small;
+  const bool forced_fits = (force_k32 && conv_k32_variant_ok(a, forced.k32)) ||
+                           (forced.family == ConvFamily::SubWino && conv_subwino_ok(a));
+  ch.takes_prologue = forced_fits || pointwise || halo != ConvTile::None;
+  ch.lds_tables = a.pro_scale && a.ws_np == 2 &&
+                  (a.taps == 1 ? conv_pw_ok(a) : halo != ConvTile::None && conv_patch3_ok(a, halo, ch.geom));
+  // whether the tile's waves own whole 64-row chunks (the 64-row tiles' waves do not): the statistics rules' premise
+  const K32Form fk = forced.k32;
+  const bool rows64 = forced_fits ? !(fk == K32Form::SplitK64x64 || fk == K32Form::SplitK64x128 ||
+                                      fk == K32Form::Small8 || fk == K32Form::S2 || fk == K32Form::S2Seg)
+                                  : pointwise || (halo != ConvTile::None && halo != ConvTile::T64x64);
+  const char* refused = conv_choose_kernel(a, forced, automatic, pointwise, rows64, halo, ch);
+  const char* operands = conv_check_operands(a);
+  ch.error = operands ? operands : refused;
+  return ch;
+}
+
+int conv2d_run(const ConvArgs& a, const ConvChoice& ch, hipStream_t st) {
+  DM_REQUIRE(!ch.error, ch.error);
+  switch (ch.family) {
+    case ConvFamily::H16: return conv2d_h16(a, st);
+    case ConvFamily::SubWino: return conv2d_subwino(a, st);
+    case ConvFamily::Wino: return conv2d_wino(a, st);
+    case ConvFamily::K32:
+    case ConvFamily::K32Small: return conv2d_k32(a, ch.k32, st);
+    case ConvFamily::Pointwise3:
+    case ConvFamily::Patch3: return conv2d_patch3(a, ch, st);
+    case ConvFamily::Patch: return conv2d_patch(a, ch.tile, ch.geom, st);
+    case ConvFamily::Im2col: break;
   }
   const int mode = conv_mode(a);
-  const int pick = conv_pick(a);
-  DM_REQUIRE(!a.gn_part || conv_can_emit_gn(a), "conv: GroupNorm statistics need a 128-row halo-patch tile, "
-                                                 "whole 64-pixel chunks and groups within 32 channels");
-  DM_REQUIRE(!a.pro_scale || (pick >= 3 && a.pro_shift && aligned16(a.pro_scale) && aligned16(a.pro_shift)),
-             "conv: the GroupNorm prologue needs a halo-patch shape (3x3 stride 1 / upsample, whole-row tiles)");
-  if (const int k32 = a.k32_resolved ? a.k32_resolved - 1 : conv_k32_pick(a)) return conv2d_k32(a, k32, st);
-  if (pick >= 3 && a.taps == 1) return conv2d_patch3(a, pick + 1, PatchGeom{}, st);  // MODE 3 (split 1x1)
-  if (pick >= 3) {
-    PatchGeom g;
-    conv_patch_pick(a, g);
-    if (conv_patch3_ok(a, pick + 1, g)) return conv2d_patch3(a, pick + 1, g, st);
-    if (pick + 1 <= 6) return conv2d_patch(a, pick + 1, g, st);
-    return launch_conv_tile<128, 128, 64, 64>(a, mode, st);  // a split-only tile that does not fit
-  }
-  DM_REQUIRE(a.upsample != 2, "conv: the sub-pixel upsample runs on the halo-patch kernel only (shape has no "
-                              "whole-row tiling)");
-  switch (pick) {
-    case 0: return launch_conv_tile<128, 128, 64, 64>(a, mode, st);
-    case 1: return launch_conv_tile<128, 64, 64, 32>(a, mode, st);
+  switch (ch.tile) {
+    case ConvTile::T128x128: return launch_conv_tile<128, 128, 64, 64>(a, mode, st);
+    case ConvTile::T128x64: return launch_conv_tile<128, 64, 64, 32>(a, mode, st);
     default: return launch_conv_tile<64, 64, 32, 32>(a, mode, st);
   }
 }
 
-// Kernel choice: 0..2 im2col tiles (128x128, 128x64, 64x64), 3..5 halo-patch
-// tiles (same shapes). The patch kernel handles 3x3 stride-1 / upsample
-// shapes whose tile covers whole rows; otherwise the im2col kernel, with the
-// 128x128 tile when it still yields >= 2 waves of blocks over 256 CUs.
-// `a.tile` 1..6 forces a configuration (tests / tuning); a forced patch tile
-// falls back to im2col when the shape does not tile.
-int conv_pick(const ConvArgs& a) {
-  if (a.tile >= 1 && a.tile <= 3) return a.tile - 1;
-  if ((a.tile == 10 || a.tile == 11) && conv_k32_ok(a)) return a.tile - 7;  // forced K = 32 split tiles (conv_k32.hip)
-  if ((a.tile == 12 || a.tile == 13) && conv_k32_variant_ok(a, a.tile - 9)) return 5;  // forced K32 split-K tiles
-  if (a.tile == 14 && conv_k32_variant_ok(a, 5)) return 8;  // forced K32 64-pixel row / segment tiles
-  if (a.tile == 15 && conv_k32_variant_ok(a, 6)) return 5;  // forced K32 small-map kernel (in-block split-K)
-  if (a.tile == 16 && conv_k32_variant_ok(a, 7)) return 8;  // forced K32 512-thread wide-map tiles
-  if (a.tile == 17 && conv_k32_variant_ok(a, 8)) return 3;  // forced K32 big-table 128 x 128 tiles
-  if (a.tile == 18 && conv_k32_variant_ok(a, 9)) return 5;  // forced K32 stride-2 tiles
-  if (a.tile == 19 && conv_k32_variant_ok(a, 10)) return 3;  // forced K32 2-D tiles of wide maps
-  if (a.tile == 20 && conv_k32_variant_ok(a, 11)) return 3;  // forced K32 64-row single-image tiles (8^2)
-  if (a.tile == 22 && conv_k32_variant_ok(a, 13)) return 5;  // forced K32 stride-2 row-segment tiles (Wout > 64)
-  if (a.tile == 23 && conv_subwino_ok(a)) return 3;  // forced sub-pixel Winograd upsample kernel (conv_subwino.hip)
-  if (conv_pw_ok(a)) {  // split 1x1: 128x128 tiles when they still give >= 2 blocks per CU, else 128x64
-    const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
-    return (a.Cout >= 128 && ((M + 127) / 128) * ((a.Cout + 127) / 128) >= 512) ? 3 : 4;
-  }
-  PatchGeom g;
-  const int p = conv_patch_pick(a, g);
-  if (p) return p - 1;
-  if (a.tile >= 4 && a.tile <= 6) return a.tile - 4;  // a forced patch tile that does not fit: its im2col shape
-  if (a.tile >= 7) return 0;                           // a forced big / segment split tile that does not fit
-  const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
-  const long b128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
-  if (a.Cout >= 128 && b128 >= 512) return 0;
-  const long b128x64 = ((M + 127) / 128) * ((a.Cout + 63) / 64);
-  if (b128x64 >= 512) return 1;
-  return 2;
-}
-
-bool conv_can_emit_gn(const ConvArgs& a) {
-  if (a.h16) return conv_h16_can_emit(a);  // the conv-half kernel: StagedEpilogue over each wave's 64-pixel chunk
-  // the split-K reduction emits them (conv_splitk_reduce_gn_kernel; after the 4 x 4 Winograd kernel, conv_k32s's own
-  // in-block reduction): one chunk per image
-  if (a.ksplit > 1)
-    return !a.upsample && a.Hout * a.Wout <= kGnPixPerChunk && a.gn_G > 0 && a.Cout % a.gn_G == 0 &&
-           a.Cout <= 1024;
-  if ((a.tile == 0 || a.tile == 23) && conv_subwino_ok(a)) return true;  // (conv_subwino_shape_ok's group rule)
-  if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a))  // StagedEpilogue over 64-pixel chunks of one image
-    return a.gn_G > 0 && a.Cout % a.gn_G == 0 && (a.Cout / a.gn_G) % 4 == 0 && a.Cout / a.gn_G <= 32;
-  // the K32 stride-2 tiles: a block's 64 rows are one 64-pixel chunk (two 32-row waves per column slice)
-  // (13: the row-segment form, 64 consecutive pixels of one output row)
-  if (a.stride == 2 && (conv_k32_pick(a) == 9 || conv_k32_pick(a) == 13))
-    return (a.Hout * a.Wout) % 64 == 0 && a.gn_G > 0 && a.Cout % a.gn_G == 0 && 32 % (a.Cout / a.gn_G) == 0;
-  // the K32 2-D tiles of wide maps: each wave's 64 rows are one tile's 64 pixels (a disjoint cover of the image;
-  // of one parity's low-res pixels for the sub-pixel upsample)
-  if (conv_k32_pick(a) == 10)
-    return a.gn_G > 0 && a.Cout % a.gn_G == 0 && 32 % (a.Cout / a.gn_G) == 0 &&
-           (a.upsample != 2 || (toggles().gn_fusion && (a.Cout / a.gn_G) % 4 == 0));
-  const int pick = conv_pick(a);
-  if (pick != 3 && pick != 4 && pick != 6 && pick != 7 && pick != 8) return false;  // waves own whole 64-row chunks
-  if (conv_k32_pick(a) && a.Cout % a.gn_G == 0 && a.Cout / a.gn_G > 32) return false;  // K32: groups within 32 columns
-  // the K32 sub-pixel upsample (128-row tiles, 64-row waves of one parity): chunks of 64 low-res pixels
-  if (a.upsample == 2) {
-    const int v = conv_k32_pick(a);
-    return (v == 1 || v == 2) && toggles().gn_fusion && (a.Hin * a.Win) % 64 == 0 && a.gn_G > 0 &&
-           a.Cout % a.gn_G == 0 && 32 % (a.Cout / a.gn_G) == 0 && (a.Cout / a.gn_G) % 4 == 0;
-  }
-  if (a.upsample || (a.ksplit > 1)) return false;
-  if (a.taps == 1 && !conv_pw_ok(a)) return false;
-  if ((a.Hout * a.Wout) % 64 != 0 || a.gn_G <= 0 || a.Cout % a.gn_G != 0) return false;
-  const int cpg = a.Cout / a.gn_G;
-  return 32 % cpg == 0;
-}
-
 // The exact kernel instantiation (matches the rocprofv3 kernel name with spaces removed).
-std::string conv_label(const ConvArgs& a) {
-  static const char* names[] = {"conv_igemm_kernel<128,128,64,64", "conv_igemm_kernel<128,64,64,32",
-                                "conv_igemm_kernel<64,64,32,32",   "conv_patch_kernel<128,128,64,64",
-                                "conv_patch_kernel<128,64,64,32",  "conv_patch_kernel<64,64,32,32",
-                                "conv_patch_kernel<256,256,128,128", "conv_patch_kernel<512,128,128,128",
-                                "conv_patch_kernel<128,128,64,64"};
-  if (a.h16) return conv_h16_label(a);
-  if ((a.tile == 0 || a.tile == 23) && conv_subwino_ok(a)) return conv_subwino_label(a);
-  if ((a.tile == 0 || a.tile == 21) && conv_wino_ok(a)) return conv_wino_label(a);
-  if (const int k32 = a.k32_resolved ? a.k32_resolved - 1 : conv_k32_pick(a)) return conv_k32_label(a, k32);
-  const int p = conv_pick(a);
-  std::string s = names[p];
-  if (p < 3) s += "," + std::to_string(conv_mode(a)) + ">";  // <BM,BN,WM,WN,MODE>
-  if (p >= 3 && a.taps == 1)  // split 1x1: conv_patch3_kernel<128,BN,64,WN,3,128,PRO,false,2>
-    return std::string(p == 3 ? "conv_patch3_kernel<128,128,64,64,3,128," : "conv_patch3_kernel<128,64,64,32,3,128,") +
-           (a.pro_scale ? "true" : "false") + ",false,2>";
-  if (p >= 3) {  // <BM,BN,WM,WN,MODE,MAXP,PRO,KSPLIT>; MAXP 288 (208 split-bf16) for 128-row tiles, 160 for 64-row
-    PatchGeom g;
-    conv_patch_pick(a, g);
-    const bool x3 = conv_patch3_ok(a, p + 1, g);
-    if (x3) s.replace(0, 17, "conv_patch3_kernel");
-    s += "," + std::to_string(a.stride == 2 ? 4 : a.upsample);
-    s += a.stride == 2 ? ",384" : p == 5 ? ",160" : p == 6 ? ",352" : p == 7 ? ",656" : p == 8 ? ",392" :
-         (x3 ? ",208" : ",288");
-    s += a.pro_scale ? ",true" : ",false";
-    s += a.ksplit > 1 ? ",true" : ",false";  // rocprofv3 prints the defaulted arguments too
-    s += x3 ? "," + std::to_string(a.ws_np) + ">" : ">";  // <..., NP>: 3 bf16x3, 2 fp16x2
+std::string conv_label(const ConvArgs& a, const ConvChoice& ch) {
+  const char* pro = a.pro_scale ? "true" : "false";
+  switch (ch.family) {
+    case ConvFamily::H16: return conv_h16_label(a, ch.h16);
+    case ConvFamily::SubWino: return conv_subwino_label(a);
+    case ConvFamily::Wino: return conv_wino_label(a);
+    case ConvFamily::K32:
+    case ConvFamily::K32Small: return conv_k32_label(a, ch.k32);
+    case ConvFamily::Pointwise3:  // conv_patch3_kernel<128,BN,64,WN,3,128,PRO,false,2>
+      return std::string("conv_patch3_kernel<") + tile_dims(ch.tile) + ",3,128," + pro + ",false,2>";
+    case ConvFamily::Im2col:  // <BM,BN,WM,WN,MODE>
+      return std::string("conv_igemm_kernel<") + tile_dims(ch.tile) + "," + std::to_string(conv_mode(a)) + ">";
+    default: break;
   }
-  return s;
+  // <BM,BN,WM,WN,MODE,MAXP,PRO,KSPLIT(,NP)>; rocprofv3 prints the defaulted arguments too. NP: 3 bf16x3, 2 fp16x2
+  const bool x3 = ch.family == ConvFamily::Patch3;
+  const int maxp = a.stride == 2                     ? kPatchS2Max
+                   : ch.tile == ConvTile::T64x64     ? kPatch3Max64  // (= kPatchMax64)
+                   : ch.tile == ConvTile::T256x256   ? kPatch3Max256
+                   : ch.tile == ConvTile::T512x128   ? kPatch3Max512
+                   : ch.tile == ConvTile::Seg128     ? kPatch3Seg
+                                                     : (x3 ? kPatch3Max128 : kPatchMax128);
+  return std::string(x3 ? "conv_patch3_kernel<" : "conv_patch_kernel<") + tile_dims(ch.tile) + "," +
+         std::to_string(a.stride == 2 ? 4 : a.upsample) + "," + std::to_string(maxp) + "," + pro +
+         (a.ksplit > 1 ? ",true" : ",false") + (x3 ? "," + std::to_string(a.ws_np) + ">" : ">");
+}
+
+// "family:variant" (dm_debug_conv_choice; tests/test_conv_dispatch_host.py)
+std::string conv_choice_name(const ConvArgs& a, const ConvChoice& ch) {
+  static const char* tiles[] = {"none", "128x128", "128x64", "64x64", "256x256", "512x128", "seg128"};
+  static const char* k32[] = {"none", "t128x128", "t128x64", "splitk64x64", "splitk64x128", "seg64", "w8", "wide512",
+                              "bigtab", "s2", "t2d", "rows64", "w4", "s2seg"};
+  switch (ch.family) {
+    case ConvFamily::Im2col: return std::string("im2col:") + tiles[(int)ch.tile];
+    case ConvFamily::Patch: return std::string("patch:") + tiles[(int)ch.tile];
+    case ConvFamily::Patch3: return std::string("patch3:") + tiles[(int)ch.tile];
+    case ConvFamily::Pointwise3: return std::string("pw3:") + tiles[(int)ch.tile];
+    case ConvFamily::K32: return std::string("k32:") + k32[(int)ch.k32];
+    case ConvFamily::K32Small: return std::string("k32small:") + k32[(int)ch.k32];
+    case ConvFamily::Wino: return a.Wout > 32 ? std::string("wino:wide") : "wino:w" + std::to_string(a.Wout);
+    case ConvFamily::SubWino: return "subwino:w" + std::to_string(a.Win);
+    case ConvFamily::H16: return ch.h16 == H16Form::T2D ? "h16:t2d" : "h16:rows";
+  }
+  return "";
 }
 
 }  // namespace dm

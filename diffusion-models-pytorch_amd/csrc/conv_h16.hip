@@ -310,7 +310,7 @@ bool rows_geom(const ConvArgs& a, PatchGeom& g) {
   if (a.Wout != 8 && a.Wout != 16 && a.Wout != 32) return false;
   return conv_patch_geom(a, 128, g) && g.P <= kHMaxP && g.TB <= 2 && g.TW == a.Wout;
 }
-// form 2's: 4 output rows x 32 columns per tile, a 6 x 34 patch (conv_k32's variant 10)
+// form 2's: 4 output rows x 32 columns per tile, a 6 x 34 patch (conv_k32's T2D)
 bool t2d_geom_h(const ConvArgs& a, PatchGeom& g) {
   if (a.Wout < 64 || a.Wout > 256 || a.Wout % 32 != 0 || a.Hout % 4 != 0) return false;
   g.TB = 1;
@@ -326,24 +326,24 @@ bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
-int conv_h16_form(const ConvArgs& a) {
-  if (a.tile < 0 || a.tile > 2) return 0;
+H16Form conv_h16_form(const ConvArgs& a) {
+  if (a.tile < 0 || a.tile > 2) return H16Form::None;
   // the covered convs
-  if (a.taps != 9 || a.stride != 1 || a.upsample != 0 || a.ksplit > 1) return 0;
-  if (a.Cin1 < kHC || a.Cin1 % kHC != 0 || a.Cin2 < 0 || a.Cin2 % kHC != 0 || a.Cout <= 0 || a.Cout % 32 != 0) return 0;
-  if (a.K != 9 * a.Cin1 + a.Cin2 || a.B <= 0 || a.Hin != a.Hout || a.Win != a.Wout) return 0;
-  if ((long)a.Hout * a.Wout < 64 || (long)a.B * a.Hout * a.Wout >= (1L << 31)) return 0;
-  if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && al16(a.ws))) return 0;
-  if (a.Cin2 > 0 && !a.x2) return 0;
-  if (!al16(a.h16_a1) || !al16(a.h16_a2)) return 0;
-  if (!staged_epilogue_ok(a)) return 0;
-  if (a.gn_part && !conv_h16_can_emit(a)) return 0;
+  if (a.taps != 9 || a.stride != 1 || a.upsample != 0 || a.ksplit > 1) return H16Form::None;
+  if (a.Cin1 < kHC || a.Cin1 % kHC != 0 || a.Cin2 < 0 || a.Cin2 % kHC != 0 || a.Cout <= 0 || a.Cout % 32 != 0) return H16Form::None;
+  if (a.K != 9 * a.Cin1 + a.Cin2 || a.B <= 0 || a.Hin != a.Hout || a.Win != a.Wout) return H16Form::None;
+  if ((long)a.Hout * a.Wout < 64 || (long)a.B * a.Hout * a.Wout >= (1L << 31)) return H16Form::None;
+  if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && al16(a.ws))) return H16Form::None;
+  if (a.Cin2 > 0 && !a.x2) return H16Form::None;
+  if (!al16(a.h16_a1) || !al16(a.h16_a2)) return H16Form::None;
+  if (!staged_epilogue_ok(a)) return H16Form::None;
+  if (a.gn_part && !conv_h16_can_emit(a)) return H16Form::None;
   PatchGeom g;
-  const int form = rows_geom(a, g) ? 1 : t2d_geom_h(a, g) ? 2 : 0;
-  return (a.tile == 0 || a.tile == form) ? form : 0;
+  const H16Form form = rows_geom(a, g) ? H16Form::Rows : t2d_geom_h(a, g) ? H16Form::T2D : H16Form::None;
+  return (a.tile == 0 || a.tile == (int)form) ? form : H16Form::None;  // (tile 1 / 2 force Rows / T2D)
 }
 
-bool conv_h16_ok(const ConvArgs& a) { return conv_h16_form(a) != 0; }
+bool conv_h16_ok(const ConvArgs& a) { return conv_h16_form(a) != H16Form::None; }
 
 // StagedEpilogue<64>'s rule: every wave's 64 rows are one 64-pixel chunk of one image, groups of 4, 8, 16 or 32 channels
 bool conv_h16_can_emit(const ConvArgs& a) {
@@ -352,12 +352,12 @@ bool conv_h16_can_emit(const ConvArgs& a) {
   return cpg == 4 || cpg == 8 || cpg == 16 || cpg == 32;
 }
 
-static const char* h16_name(int form, bool longk) {
-  return form == 2 ? (longk ? "conv_h16_kernel<true,32>" : "conv_h16_kernel<true,64>")
+static const char* h16_name(H16Form form, bool longk) {
+  return form == H16Form::T2D ? (longk ? "conv_h16_kernel<true,32>" : "conv_h16_kernel<true,64>")
                    : (longk ? "conv_h16_kernel<false,32>" : "conv_h16_kernel<false,64>");
 }
 
-std::string conv_h16_label(const ConvArgs& a) { return h16_name(conv_h16_form(a), a.Cin1 / kHC > kHFlush); }
+std::string conv_h16_label(const ConvArgs& a, H16Form form) { return h16_name(form, a.Cin1 / kHC > kHFlush); }
 
 int conv_h16_image(const ConvArgs& a, _Float16* plane1, _Float16* plane2, hipStream_t st) {
   auto launch = [&](const float* x, int pitch, int C, long npix, int hw, const float* sc, const float* sh, int pro,
@@ -396,17 +396,17 @@ int conv_h16_image(const ConvArgs& a, _Float16* plane1, _Float16* plane2, hipStr
 }
 
 int conv2d_h16(const ConvArgs& a, hipStream_t st) {
-  const int form = conv_h16_form(a);
-  DM_REQUIRE(form != 0 && a.h16_a1 && (a.Cin2 == 0 || a.h16_a2),
+  const H16Form form = conv_h16_form(a);
+  DM_REQUIRE(form != H16Form::None && a.h16_a1 && (a.Cin2 == 0 || a.h16_a2),
              "conv_h16: needs the fp16 image plane(s), fp16x2 split weights and a covered 3x3 stride-1 shape");
   PatchGeom g;
-  if (form == 1) rows_geom(a, g);
+  if (form == H16Form::Rows) rows_geom(a, g);
   else t2d_geom_h(a, g);
   const int M = a.B * a.Hout * a.Wout;
   const int blocks = ceil_div(M, 128) * ceil_div(a.Cout, 128);
   const bool longk = a.Cin1 / kHC > kHFlush;
-  if (form == 1 && longk) hipLaunchKernelGGL((conv_h16_kernel<false, 32>), dim3(blocks), dim3(512), 0, st, a, g);
-  else if (form == 1) hipLaunchKernelGGL((conv_h16_kernel<false, 64>), dim3(blocks), dim3(256), 0, st, a, g);
+  if (form == H16Form::Rows && longk) hipLaunchKernelGGL((conv_h16_kernel<false, 32>), dim3(blocks), dim3(512), 0, st, a, g);
+  else if (form == H16Form::Rows) hipLaunchKernelGGL((conv_h16_kernel<false, 64>), dim3(blocks), dim3(256), 0, st, a, g);
   else if (longk) hipLaunchKernelGGL((conv_h16_kernel<true, 32>), dim3(blocks), dim3(512), 0, st, a, g);
   else hipLaunchKernelGGL((conv_h16_kernel<true, 64>), dim3(blocks), dim3(256), 0, st, a, g);
   note_launch(h16_name(form, longk));

@@ -46,7 +46,7 @@ constexpr int kRowH = 80;       // LDS row pitch in fp16: 160 B; [piece][k-group
 constexpr int kMaxP = 208;      // patch pixels: 32^2 maps 6 x 34, 16^2 maps 10 x 18, 8^2 maps 2 x 10 x 10
 constexpr int kMaxPW = 392;     // 512-thread wide-map tiles: 3 x 130 (128-pixel row segments), 4 x 66 (64^2 maps)
 constexpr int kTab = 2048;      // GroupNorm table floats (per image of the tile: its channels' scales, then the shifts)
-constexpr int kTabBig = 8192;   // variant 8: up to 2048 input channels of two images (one block per CU)
+constexpr int kTabBig = 8192;   // BigTab: up to 2048 input channels of two images (one block per CU)
 constexpr int kStats = 128;     // (image, group) pairs of the in-kernel finalize
 
 
@@ -82,7 +82,7 @@ __device__ unsigned long long g_k32_stamps[65536][8];
 // patch pixels for every tap, as in the stride-1 patch (conflict-free ds_read_b128).
 // T2D: 2-D tiles of wide maps (ADM's 64^2 .. 256^2): a 128-row tile is TH = 4 output rows x TW = 32 columns,
 // the GEMM row index m enumerating pixels tile by tile (t2d_pixel), so the patch is the 32^2 maps' 6 x 34 and the
-// kernel runs as variant 1 does there; the epilogue, the shortcut segment and the GroupNorm chunks (64 rows of
+// kernel runs as T128x128 does there; the epilogue, the shortcut segment and the GroupNorm chunks (64 rows of
 // one tile: a disjoint cover of the image) map m back to the pixel.
 template <int BM, int BN, int WM, int WN, bool PRO, bool KSPLIT, bool SUB = false, int NT = 256, int MAXP = kMaxP,
           int TABF = kTab, bool S2 = false, bool T2D = false>
@@ -912,13 +912,14 @@ extern "C" int dm_debug_k32_stamps(void* host, int nblocks) {
 }
 #endif
 
-// Variants: 1 = 128 x 128 tiles, 2 = 128 x 64 (whole K), 3 = 64 x 64 and 4 = 64 x 128 split-K tiles,
-// 5 = 64 x 128 tiles of one image row or 64-pixel row segment (ADM's 64^2 .. 256^2 maps), 6 = the small-map
-// kernel (64 x 64 tiles of four 4 x 4 images, K split in two inside the block; the plan's ksplit = 2),
-// 7 = 512-thread 128 x 128 tiles of 64 x 32 wave tiles (wide maps), 8 = variant 1 / its sub-pixel form with a
-// 32 KB GroupNorm table (inputs of up to 2048 channels at two images per tile; one block per CU), 9 = the
-// stride-2 downsample (64 x 128 tiles of 8 waves of 32 x 32 over whole output rows, one block per CU),
-// 13 = variant 9's kernel over 64-pixel segments of one output row wider than 64 pixels (s2seg_geom).
+// The forms (K32Form): T128x128, T128x64 (whole K), SplitK64x64 and SplitK64x128 split-K tiles, Seg64 = 64 x 128
+// tiles of one image row or 64-pixel row segment (ADM's 64^2 .. 256^2 maps), Small8 / Small4 = the small-map kernel
+// (64 x 64 tiles of four 4 x 4 images, K split in two inside the block; the plan's ksplit = 2), Wide512 = 512-thread
+// 128 x 128 tiles of 64 x 32 wave tiles (wide maps), BigTab = T128x128 / its sub-pixel form with a 32 KB GroupNorm
+// table (inputs of up to 2048 channels at two images per tile; one block per CU), S2 = the stride-2 downsample
+// (64 x 128 tiles of 8 waves of 32 x 32 over whole output rows, one block per CU), S2Seg = S2's kernel over 64-pixel
+// segments of one output row wider than 64 pixels (s2seg_geom), T2D = 2-D tiles of wide maps, Rows64 = 64-row
+// tiles of one 8 x 8 image.
 static bool conv_k32s_ok(const ConvArgs& a) {
   if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && a.upsample == 0)) return false;
   if (a.ksplit != 2 || a.Hout * a.Wout != 16 || a.Hin != a.Hout || a.Win != a.Wout) return false;
@@ -936,7 +937,7 @@ static bool conv_k32s_ok(const ConvArgs& a) {
 
 static bool t2d_geom(const ConvArgs& a, PatchGeom& g);
 
-// variant 13's geometry: one output row x 64 consecutive columns per 64-row tile (Wout > 64), a patch of 3 input
+// S2Seg's geometry: one output row x 64 consecutive columns per 64-row tile (Wout > 64), a patch of 3 input
 // rows x 2 (64 + 1) parity-split columns from input column 2 x0 - 1 (2 x0 with s2_pad0): 390 pixels
 static bool s2seg_geom(const ConvArgs& a, PatchGeom& g) {
   if (a.taps != 9 || a.stride != 2 || a.upsample || a.Cin2) return false;
@@ -950,85 +951,82 @@ static bool s2seg_geom(const ConvArgs& a, PatchGeom& g) {
   return true;
 }
 
-int conv_k32_variant_ok(const ConvArgs& a, int v) {
-  if (v == 6 || v == 12) return conv_k32s_ok(a) ? 1 : 0;
-  if (v == 11) {  // 64-row tiles of one <= 64-pixel image (8^2 maps), 4 waves of 32 x 64
-    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && a.upsample == 0)) return 0;
-    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1 || a.K != 9 * a.Cin1 + a.Cin2) return 0;
-    if (a.Hout * a.Wout != 64 || a.Wout % 8 != 0) return 0;
+bool conv_k32_variant_ok(const ConvArgs& a, K32Form v) {
+  using F = K32Form;
+  if (v == F::Small8 || v == F::Small4) return conv_k32s_ok(a);
+  if (v == F::Rows64) {  // 64-row tiles of one <= 64-pixel image (8^2 maps), 4 waves of 32 x 64
+    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && a.upsample == 0)) return false;
+    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1 || a.K != 9 * a.Cin1 + a.Cin2) return false;
+    if (a.Hout * a.Wout != 64 || a.Wout % 8 != 0) return false;
     PatchGeom g;
-    if (!conv_patch_geom(a, 64, g) || g.P > kMaxP || g.TB != 1) return 0;
-    if (a.pro_scale && 2 * a.Cin1 > kTab) return 0;
-    if (a.gin_part && a.gin_G > kStats) return 0;
-    return staged_epilogue_ok(a) ? 1 : 0;
+    if (!conv_patch_geom(a, 64, g) || g.P > kMaxP || g.TB != 1) return false;
+    if (a.pro_scale && 2 * a.Cin1 > kTab) return false;
+    if (a.gin_part && a.gin_G > kStats) return false;
+    return staged_epilogue_ok(a);
   }
-  if (v == 10) {
-    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale)) return 0;
-    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1) return 0;
-    if (a.upsample == 2 ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return 0;
+  if (v == F::T2D) {
+    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale)) return false;
+    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1) return false;
+    if (a.upsample == 2 ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return false;
     PatchGeom g;
-    if (!t2d_geom(a, g)) return 0;
-    if (a.pro_scale && 2 * a.Cin1 > kTab) return 0;
-    if (a.gin_part && a.gin_G > kStats) return 0;
-    return staged_epilogue_ok(a) ? 1 : 0;
+    if (!t2d_geom(a, g)) return false;
+    if (a.pro_scale && 2 * a.Cin1 > kTab) return false;
+    if (a.gin_part && a.gin_G > kStats) return false;
+    return staged_epilogue_ok(a);
   }
-  if (v == 9 || v == 13) {
-    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 2 && a.upsample == 0)) return 0;
-    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 != 0 || a.ksplit > 1 || a.K != 9 * a.Cin1) return 0;
-    if (a.Wout % 8 != 0) return 0;
+  if (v == F::S2 || v == F::S2Seg) {
+    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 2 && a.upsample == 0)) return false;
+    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 != 0 || a.ksplit > 1 || a.K != 9 * a.Cin1) return false;
+    if (a.Wout % 8 != 0) return false;
     PatchGeom g;
-    if (!(v == 13 ? s2seg_geom(a, g) : conv_patch_geom(a, 64, g)) || g.P > kMaxPW || g.TB > 2) return 0;
-    if (a.pro_scale && 2 * g.TB * a.Cin1 > kTab) return 0;
-    if (a.gin_part && g.TB * a.gin_G > kStats) return 0;
-    return staged_epilogue_ok(a) ? 1 : 0;
+    if (!(v == F::S2Seg ? s2seg_geom(a, g) : conv_patch_geom(a, 64, g)) || g.P > kMaxPW || g.TB > 2) return false;
+    if (a.pro_scale && 2 * g.TB * a.Cin1 > kTab) return false;
+    if (a.gin_part && g.TB * a.gin_G > kStats) return false;
+    return staged_epilogue_ok(a);
   }
-  if (v == 7) {  // 128-row tiles of 512 threads over one image's 128-pixel row segment or two 64-pixel rows
+  if (v == F::Wide512) {  // 128-row tiles of 512 threads over one image's 128-pixel row segment or two 64-pixel rows
     const bool sub = a.upsample == 2;
-    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && (a.upsample == 0 || sub))) return 0;
-    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1) return 0;
-    if (sub ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return 0;
+    if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && (a.upsample == 0 || sub))) return false;
+    if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0 || a.ksplit > 1) return false;
+    if (sub ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return false;
     // or whole rows of up to two images of a narrower map (8^2 .. 32^2: 8 waves per CU where 256 blocks of 4
     // waves leave one wave per SIMD)
     const int wt = sub ? a.Win : a.Wout;
     const bool wide = wt >= 64 && (wt > 128 ? wt % 128 == 0 : 128 % wt == 0);
     const bool narrow = wt < 64 && wt % 8 == 0 && 128 % wt == 0;
-    if (!wide && !narrow) return 0;
+    if (!wide && !narrow) return false;
     PatchGeom g;
-    if (!conv_patch_geom(a, 128, g) || g.P > kMaxPW || g.TB > (wide ? 1 : 2)) return 0;
-    if (a.pro_scale && 2 * g.TB * a.Cin1 > kTab) return 0;
-    if (a.gin_part && g.TB * a.gin_G > kStats) return 0;
-    return staged_epilogue_ok(a) ? 1 : 0;
+    if (!conv_patch_geom(a, 128, g) || g.P > kMaxPW || g.TB > (wide ? 1 : 2)) return false;
+    if (a.pro_scale && 2 * g.TB * a.Cin1 > kTab) return false;
+    if (a.gin_part && g.TB * a.gin_G > kStats) return false;
+    return staged_epilogue_ok(a);
   }
   const bool sub = a.upsample == 2;  // sub-pixel nearest-2x + 3x3: 4 parity convs of 4 taps
-  if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && (a.upsample == 0 || sub))) return 0;
-  if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0) return 0;
-  if (sub ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return 0;
-  const bool split = v == 3 || v == 4, seg = v == 5, big = v == 8;
-  if (split && sub) return 0;
+  if (!(a.ws && a.ws_np == 2 && a.ws_rowscale && a.taps == 9 && a.stride == 1 && (a.upsample == 0 || sub))) return false;
+  if (a.Cin1 < kC || a.Cin1 % kC != 0 || a.Cin2 % kC != 0) return false;
+  if (sub ? (a.Cin2 != 0 || a.K != 4 * a.Cin1) : a.K != 9 * a.Cin1 + a.Cin2) return false;
+  const bool split = v == F::SplitK64x64 || v == F::SplitK64x128, seg = v == F::Seg64, big = v == F::BigTab;
+  if (split && sub) return false;
   const int bm = (split || seg) ? 64 : BM_K32;
-  if (split ? !(a.ksplit > 1 && a.kpart && a.ksplit <= a.Cin1 / kC) : a.ksplit > 1) return 0;
+  if (split ? !(a.ksplit > 1 && a.kpart && a.ksplit <= a.Cin1 / kC) : a.ksplit > 1) return false;
   const int wt = sub ? a.Win : a.Wout;  // tiled width
-  if (seg ? (wt < 64 || wt % 64 != 0) : (wt > bm || bm % wt != 0)) return 0;
+  if (seg ? (wt < 64 || wt % 64 != 0) : (wt > bm || bm % wt != 0)) return false;
   PatchGeom g;
-  if (!conv_patch_geom(a, bm, g) || g.P > kMaxP || g.TB > (split ? 4 : 2) || (seg && g.TB != 1)) return 0;
+  if (!conv_patch_geom(a, bm, g) || g.P > kMaxP || g.TB > (split ? 4 : 2) || (seg && g.TB != 1)) return false;
   const int nch = a.Cin1 / kC, tab_c = split ? ceil_div(nch, a.ksplit) * kC : a.Cin1;
-  if (a.pro_scale && 2 * g.TB * tab_c > (big ? kTabBig : kTab)) return 0;
-  if (a.gin_part && g.TB * a.gin_G > kStats) return 0;
+  if (a.pro_scale && 2 * g.TB * tab_c > (big ? kTabBig : kTab)) return false;
+  if (a.gin_part && g.TB * a.gin_G > kStats) return false;
   if (split) {  // raw partial sums with 16-byte stores
-    if (a.Cout % 4 != 0 || (reinterpret_cast<uintptr_t>(a.kpart) & 15) != 0) return 0;
-    return 1;
+    if (a.Cout % 4 != 0 || (reinterpret_cast<uintptr_t>(a.kpart) & 15) != 0) return false;
+    return true;
   }
-  if (wt % 8 != 0) return 0;
-  return staged_epilogue_ok(a) ? 1 : 0;  // the epilogue's 16-byte loads / stores of 4 consecutive channels
+  if (wt % 8 != 0) return false;
+  return staged_epilogue_ok(a);  // the epilogue's 16-byte loads / stores of 4 consecutive channels
 }
 
-bool conv_k32_ok(const ConvArgs& a) { return conv_k32_variant_ok(a, 1) != 0; }
+static bool conv_k32_ok(const ConvArgs& a) { return conv_k32_variant_ok(a, K32Form::T128x128); }
 
-// Which conv_k32 variant runs this conv, 0 = none. Forced by tile 10 / 11 (128-row tiles) and 12 / 13
-// (split-K 64-row tiles); otherwise it replaces conv_patch3's fp16x2 tiles for 3x3 stride-1 convs. The plan
-// toggles (Toggles: DM_CONV_K32S, DM_CONV_K32S2, DM_CONV_K32T2, DM_K32_8X, DM_K32S_W4) keep the paths each form
-// replaced as its test oracle.
-// variant 10's geometry: 4 output rows x 32 columns per 128-row tile, a 6 x 34 patch
+// T2D's geometry: 4 output rows x 32 columns per 128-row tile, a 6 x 34 patch
 static bool t2d_geom(const ConvArgs& a, PatchGeom& g) {
   // tiles over the output map, or over the low-res map of the sub-pixel upsample (4 parities x 4 taps)
   const bool sub = a.upsample == 2;
@@ -1044,65 +1042,84 @@ static bool t2d_geom(const ConvArgs& a, PatchGeom& g) {
   return true;
 }
 
-int conv_k32_pick(const ConvArgs& a) {
-  if (a.tile >= 10 && a.tile <= 20) return conv_k32_variant_ok(a, a.tile - 9) ? a.tile - 9 : 0;
-  if (a.tile == 22) return conv_k32_variant_ok(a, 13) ? 13 : 0;
-  if (a.tile != 0) return 0;
+// The automatic choice (conv_choose handles a forced form): which form runs this conv, None = not this kernel. It
+// replaces conv_patch3's fp16x2 tiles (halo: the conv's halo-patch tile). The plan toggles (Toggles: DM_CONV_K32S,
+// DM_CONV_K32S2, DM_CONV_K32T2, DM_K32_8X, DM_K32S_W4) keep the paths each form replaced as its test oracle.
+K32Form k32_choose(const ConvArgs& a, ConvTile halo) {
+  using F = K32Form;
+  const bool halo128 = halo == ConvTile::T128x128 || halo == ConvTile::T128x64;  // a 128-row halo-patch tile
   if (a.stride == 2) {  // at least one block per CU (the nominal batch keeps the choice batch-invariant)
     const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
-    if (toggles().k32_s2 && conv_k32_variant_ok(a, 9) && (M / 64) * ((a.Cout + 127) / 128) >= 256) return 9;
+    if (toggles().k32_s2 && conv_k32_variant_ok(a, F::S2) && (M / 64) * ((a.Cout + 127) / 128) >= 256) return F::S2;
     // outputs wider than 64 pixels: row segments, for the bottom/right-padded form only (the symmetric wide
     // downsamples keep the im2col kernel). A shape-only choice: batch-invariant.
-    return a.s2_pad0 && toggles().k32_s2 && conv_k32_variant_ok(a, 13) ? 13 : 0;
+    return a.s2_pad0 && toggles().k32_s2 && conv_k32_variant_ok(a, F::S2Seg) ? F::S2Seg : F::None;
   }
   // split-K convs of maps of <= 16 pixels: 64 x 128 tiles (4x4 maps at B = 256, K split 2: 32.5 us vs
   // 34.2 us for 64 x 64 and for conv_patch3's 64 x 64 split tiles)
   if (a.ksplit > 1) {
-    if (toggles().k32_small && conv_k32_variant_ok(a, 6)) return toggles().k32s_w4 ? 12 : 6;
-    return conv_k32_variant_ok(a, 4) ? 4 : conv_k32_variant_ok(a, 3) ? 3 : 0;
+    if (toggles().k32_small && conv_k32_variant_ok(a, F::Small8)) return toggles().k32s_w4 ? F::Small4 : F::Small8;
+    return conv_k32_variant_ok(a, F::SplitK64x128) ? F::SplitK64x128 : conv_k32_variant_ok(a, F::SplitK64x64) ? F::SplitK64x64 : F::None;
   }
   if (!conv_k32_ok(a)) {
     // maps whose whole-row 128-row tiles do not fit the patch image (64^2 .. 256^2): 128-pixel row segments /
     // two-row tiles of 8 waves, else 64-pixel rows / segments
     const int wt = a.upsample == 2 ? a.Win : a.Wout;
-    if (wt >= 64 && toggles().k32_t2d && conv_k32_variant_ok(a, 10)) return 10;
-    if (wt >= 64 && conv_k32_variant_ok(a, 7)) return 7;
-    if (wt >= 64) return conv_k32_variant_ok(a, 5) ? 5 : 0;
+    if (wt >= 64 && toggles().k32_t2d && conv_k32_variant_ok(a, F::T2D)) return F::T2D;
+    if (wt >= 64 && conv_k32_variant_ok(a, F::Wide512)) return F::Wide512;
+    if (wt >= 64) return conv_k32_variant_ok(a, F::Seg64) ? F::Seg64 : F::None;
     // 128-row tiles whose GroupNorm tables do not fit kTab: the big-table instantiation (one block per CU)
-    const int p = conv_pick(a);
-    return ((p == 3 || p == 4) && conv_k32_variant_ok(a, 8)) ? 8 : 0;
+    return (halo128 && conv_k32_variant_ok(a, F::BigTab)) ? F::BigTab : F::None;
   }
-  const int p = conv_pick(a);
-  if (p != 3 && p != 4) return 0;
+  if (!halo128) return F::None;
   // 8^2 maps on 64-row single-image tiles (two blocks per CU where 128 x 128 tiles give one; bit-identical):
   // C3 A/B +0.3 % / +0.25 % over two sessions' alternations; DM_K32_8X=0 keeps the 128 x 128 two-image tiles
-  if (toggles().k32_8x && conv_k32_variant_ok(a, 11)) return 11;
+  if (toggles().k32_8x && conv_k32_variant_ok(a, F::Rows64)) return F::Rows64;
   // 128 x 128 tiles down to one block per CU (measured on 8^2 maps at B = 256: 256 blocks of 128 x 128 beat
   // 512 of 128 x 64 by 6 %); the nominal batch (pick_B) keeps the choice batch-invariant
   const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
-  return ((M + 127) / 128) * ((a.Cout + 127) / 128) >= 256 ? 1 : 2;
+  return ((M + 127) / 128) * ((a.Cout + 127) / 128) >= 256 ? F::T128x128 : F::T128x64;
+}
+
+// Statistics from the epilogue, per form (ksplit <= 1; the split-K forms' come from their reduction):
+bool conv_k32_can_emit(const ConvArgs& a, K32Form v, bool rows64) {
+  using F = K32Form;
+  const bool groups = a.gn_G > 0 && a.Cout % a.gn_G == 0 && 32 % (a.Cout / a.gn_G) == 0;
+  // the stride-2 tiles: a block's 64 rows are one 64-pixel chunk (two 32-row waves per column slice); S2Seg: 64
+  // consecutive pixels of one output row
+  if (v == F::S2 || v == F::S2Seg) return (a.Hout * a.Wout) % 64 == 0 && groups;
+  // the 2-D tiles of wide maps: each wave's 64 rows are one tile's 64 pixels (a disjoint cover of the image; of one
+  // parity's low-res pixels for the sub-pixel upsample)
+  if (v == F::T2D) return groups && (a.upsample != 2 || (toggles().gn_fusion && (a.Cout / a.gn_G) % 4 == 0));
+  if (!rows64 || !groups) return false;  // waves own whole 64-row chunks, groups within 32 columns
+  // the sub-pixel upsample (128-row tiles, 64-row waves of one parity): chunks of 64 low-res pixels
+  if (a.upsample == 2)
+    return (v == F::T128x128 || v == F::T128x64) && toggles().gn_fusion && (a.Hin * a.Win) % 64 == 0 &&
+           (a.Cout / a.gn_G) % 4 == 0;
+  return !a.upsample && (a.Hout * a.Wout) % 64 == 0;
 }
 
 // rocprofv3's name of the instantiation conv2d_k32 launches (spaces removed)
-std::string conv_k32_label(const ConvArgs& a, int v) {
-  if (v == 6 || v == 12)
-    return std::string("conv_k32s_kernel<") + (a.pro_scale || a.gin_part ? "true," : "false,") + (v == 12 ? "4>" : "8>");
-  if (v == 7)
+std::string conv_k32_label(const ConvArgs& a, K32Form v) {
+  using F = K32Form;
+  if (v == F::Small8 || v == F::Small4)
+    return std::string("conv_k32s_kernel<") + (a.pro_scale || a.gin_part ? "true," : "false,") + (v == F::Small4 ? "4>" : "8>");
+  if (v == F::Wide512)
     return std::string("conv_k32_kernel<128,128,64,32,") + (a.pro_scale ? "true," : "false,") + "false," +
            (a.upsample == 2 ? "true,512>" : "false,512>");
-  if (v == 8)
+  if (v == F::BigTab)
     return std::string("conv_k32_kernel<128,128,64,64,") + (a.pro_scale ? "true," : "false,") + "false," +
            (a.upsample == 2 ? "true,256,208,8192>" : "false,256,208,8192>");
-  if (v == 9 || v == 13)
+  if (v == F::S2 || v == F::S2Seg)
     return std::string("conv_k32_kernel<64,128,32,32,") + (a.pro_scale ? "true," : "false,") + "false,false,512,392,2048,true>";
-  if (v == 11) return std::string("conv_k32_kernel<64,128,32,64,") + (a.pro_scale ? "true," : "false,") + "false,false>";
-  if (v == 10)
+  if (v == F::Rows64) return std::string("conv_k32_kernel<64,128,32,64,") + (a.pro_scale ? "true," : "false,") + "false,false>";
+  if (v == F::T2D)
     return std::string("conv_k32_kernel<128,128,64,64,") + (a.pro_scale ? "true," : "false,") + "false," +
            (a.upsample == 2 ? "true" : "false") + ",256,208,2048,false,true>";
   static const char* names[] = {"", "conv_k32_kernel<128,128,64,64,", "conv_k32_kernel<128,64,64,32,",
                                 "conv_k32_kernel<64,64,32,32,", "conv_k32_kernel<64,128,32,64,",
                                 "conv_k32_kernel<64,128,32,64,"};
-  return std::string(names[v]) + (a.pro_scale ? "true," : "false,") + (v == 3 || v == 4 ? "true," : "false,") +
+  return std::string(names[(int)v]) + (a.pro_scale ? "true," : "false,") + (v == F::SplitK64x64 || v == F::SplitK64x128 ? "true," : "false,") +
          (a.upsample == 2 ? "true>" : "false>");
 }
 
@@ -1131,14 +1148,15 @@ static void launch_k32(const ConvArgs& a, const PatchGeom& g, hipStream_t st) {
                        dim3(NT), 0, st, a, g);
 }
 
-int conv2d_k32(const ConvArgs& a, int v, hipStream_t st) {
-  DM_REQUIRE(v >= 1 && v <= 13 && conv_k32_variant_ok(a, v), "conv: shape not supported by the K = 32 split kernel");
+int conv2d_k32(const ConvArgs& a, K32Form v, hipStream_t st) {
+  using F = K32Form;
+  DM_REQUIRE(v != F::None && conv_k32_variant_ok(a, v), "conv: shape not supported by the K = 32 split kernel");
   PatchGeom g;
-  if (v == 6 || v == 12) {  // the small-map kernel: 8 waves (6), or its 4-wave form (12, one wave per SIMD)
+  if (v == F::Small8 || v == F::Small4) {  // the small-map kernel: 8 waves (6), or its 4-wave form (12, one wave per SIMD)
     conv_patch_geom(a, 64, g);
     const int blocks = ceil_div(a.B * a.Hout * a.Wout, 64) * (a.Cout / 64);
     const bool pro = a.pro_scale || a.gin_part;
-    if (v == 12) {
+    if (v == F::Small4) {
       if (pro) hipLaunchKernelGGL((conv_k32s_kernel<true, 4>), dim3(blocks), dim3(256), 0, st, a, g);
       else hipLaunchKernelGGL((conv_k32s_kernel<false, 4>), dim3(blocks), dim3(256), 0, st, a, g);
       note_launch(pro ? "conv_k32s_kernel<true,4>" : "conv_k32s_kernel<false,4>");
@@ -1150,29 +1168,29 @@ int conv2d_k32(const ConvArgs& a, int v, hipStream_t st) {
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  if (v == 10) {
+  if (v == F::T2D) {
     t2d_geom(a, g);
     launch_k32<128, 128, 64, 64, false, 256, kMaxP, kTab, false, true>(a, g, st);
     DM_LAUNCH_CHECK();
     return DM_OK;
   }
-  if (v == 13) s2seg_geom(a, g);
-  else conv_patch_geom(a, (v >= 3 && v <= 6) || v == 9 || v == 11 ? 64 : BM_K32, g);
-  if (v == 13) note_launch("conv_k32_kernel<64,128,32,32,...,true> (stride-2 row segments)");
+  if (v == F::S2Seg) s2seg_geom(a, g);
+  else conv_patch_geom(a, v == F::SplitK64x64 || v == F::SplitK64x128 || v == F::Seg64 || v == F::S2 || v == F::Rows64 ? 64 : BM_K32, g);
+  if (v == F::S2Seg) note_launch("conv_k32_kernel<64,128,32,32,...,true> (stride-2 row segments)");
   switch (v) {
-    case 11: launch_k32<64, 128, 32, 64, false>(a, g, st); break;
-    case 13:  // variant 9's instantiation over s2seg_geom's tiles
-    case 9: launch_k32<64, 128, 32, 32, false, 512, kMaxPW, kTab, true>(a, g, st); break;
-    case 8: launch_k32<128, 128, 64, 64, false, 256, kMaxP, kTabBig>(a, g, st); break;
-    case 7: launch_k32<128, 128, 64, 32, false, 512, kMaxPW>(a, g, st); break;
-    case 1: launch_k32<128, 128, 64, 64, false>(a, g, st); break;
-    case 2: launch_k32<128, 64, 64, 32, false>(a, g, st); break;
-    case 3: launch_k32<64, 64, 32, 32, true>(a, g, st); break;
-    case 4: launch_k32<64, 128, 32, 64, true>(a, g, st); break;
+    case F::Rows64: launch_k32<64, 128, 32, 64, false>(a, g, st); break;
+    case F::S2Seg:  // S2's instantiation over s2seg_geom's tiles
+    case F::S2: launch_k32<64, 128, 32, 32, false, 512, kMaxPW, kTab, true>(a, g, st); break;
+    case F::BigTab: launch_k32<128, 128, 64, 64, false, 256, kMaxP, kTabBig>(a, g, st); break;
+    case F::Wide512: launch_k32<128, 128, 64, 32, false, 512, kMaxPW>(a, g, st); break;
+    case F::T128x128: launch_k32<128, 128, 64, 64, false>(a, g, st); break;
+    case F::T128x64: launch_k32<128, 64, 64, 32, false>(a, g, st); break;
+    case F::SplitK64x64: launch_k32<64, 64, 32, 32, true>(a, g, st); break;
+    case F::SplitK64x128: launch_k32<64, 128, 32, 64, true>(a, g, st); break;
     default: launch_k32<64, 128, 32, 64, false>(a, g, st); break;
   }
   DM_LAUNCH_CHECK();
-  if (v == 3 || v == 4) return conv_splitk_reduce(a, st);
+  if (v == F::SplitK64x64 || v == F::SplitK64x128) return conv_splitk_reduce(a, st);
   return DM_OK;
 }
 

@@ -330,6 +330,12 @@ __global__ void __launch_bounds__(1024) conv_splitk_reduce_gn_kernel(ConvArgs a)
 
 }  // namespace
 
+// the reduction emits the statistics (conv_splitk_reduce_gn_kernel; after the 4 x 4 Winograd kernel, conv_k32s's own
+// in-block reduction): one chunk per image
+bool conv_splitk_can_emit(const ConvArgs& a) {
+  return !a.upsample && a.Hout * a.Wout <= kGnPixPerChunk && a.gn_G > 0 && a.Cout % a.gn_G == 0 && a.Cout <= 1024;
+}
+
 int conv_splitk_reduce(const ConvArgs& a, hipStream_t st) {
   if (a.gn_part) {
     DM_REQUIRE(a.Hout * a.Wout <= kGnPixPerChunk && a.gn_G > 0 && a.Cout % a.gn_G == 0 && a.Cout <= 1024,
@@ -371,8 +377,7 @@ int launch_patch(const ConvArgs& a, const PatchGeom& g, hipStream_t st) {
   const bool sub = a.upsample == 2;
   const int M = sub ? a.B * a.Hin * a.Win : a.B * a.Hout * a.Wout;
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  DM_REQUIRE(ks == 1 || (!a.upsample && a.kpart && ks <= a.Cin1 / kBK),
-             "conv: split-K needs a stride-1 3x3 conv, a workspace and at most one split per channel chunk");
+  if (const char* e = conv_patch_refuses(a)) DM_REQUIRE(false, e);
   const int blocks = ceil_div(M, BM) * ceil_div(a.Cout, BN) * (sub ? 4 : 1) * ks;
   if (sub)
     launch_patch_mode<BM, BN, WM, WN, 2, MAXP>(a, g, blocks, st);
@@ -454,47 +459,64 @@ bool conv_patch_geom(const ConvArgs& a, int BM, PatchGeom& g) {
 }
 
 
-int conv_patch_pick(const ConvArgs& a, PatchGeom& g) {
+const char* conv_patch_refuses(const ConvArgs& a) {
+  if (a.ksplit > 1 && !(!a.upsample && a.kpart && a.ksplit <= a.Cin1 / kBK))
+    return "conv: split-K needs a stride-1 3x3 conv, a workspace and at most one split per channel chunk";
+  return nullptr;
+}
+
+// forced: None, the automatic choice; T128x128 / T128x64 / T64x64 / T256x256 / T512x128 / Seg128: that tile or none
+ConvTile conv_patch_pick(const ConvArgs& a, ConvTile forced, PatchGeom& g) {
+  using T = ConvTile;
+  const bool automatic = forced == T::None;
   if (a.stride == 2) {  // only the fp16x2 split kernel has a stride-2 mode (64-row tiles)
-    if (!(a.ws && a.ws_np == 2) || (a.tile != 0 && a.tile != 6)) return 0;
-    return conv_patch_geom(a, 64, g) && g.P <= kPatchS2Max ? 6 : 0;
+    if (!(a.ws && a.ws_np == 2) || (!automatic && forced != T::T64x64)) return T::None;
+    return conv_patch_geom(a, 64, g) && g.P <= kPatchS2Max ? T::T64x64 : T::None;
   }
-  // big-tile fp16x2 split kernels (one wave per SIMD): forced by tile 7 / 8 only (for now)
-  if (a.tile == 7 || a.tile == 8) {
-    if (!(a.ws && a.ws_np == 2)) return 0;
-    if (a.tile == 7) return conv_patch_geom(a, 256, g) && g.P <= kPatch3Max256 ? 7 : 0;
-    return conv_patch_geom(a, 512, g) && g.P <= kPatch3Max512 ? 8 : 0;
+  // big-tile fp16x2 split kernels (one wave per SIMD): forced only (for now)
+  if (forced == T::T256x256 || forced == T::T512x128) {
+    if (!(a.ws && a.ws_np == 2)) return T::None;
+    if (forced == T::T256x256) return conv_patch_geom(a, 256, g) && g.P <= kPatch3Max256 ? forced : T::None;
+    return conv_patch_geom(a, 512, g) && g.P <= kPatch3Max512 ? forced : T::None;
   }
   // wide maps (ADM 256^2 / 128^2): 128-pixel row segments on the fp16x2 split kernel
   {
     const bool sub = a.upsample == 2;
     const int Wo = sub ? a.Win : a.Wout;
     if (Wo > 128) {
-      if (!(a.ws && a.ws_np == 2) || (a.tile != 0 && a.tile != 9)) return 0;
-      return conv_patch_geom(a, 128, g) && g.P <= kPatch3Seg ? 9 : 0;
+      if (!(a.ws && a.ws_np == 2) || (!automatic && forced != T::Seg128)) return T::None;
+      return conv_patch_geom(a, 128, g) && g.P <= kPatch3Seg ? T::Seg128 : T::None;
     }
   }
   // the split-bf16 kernel's LDS image holds fewer patch pixels at 128-row tiles
   const int max128 = a.ws ? kPatch3Max128 : kPatchMax128, max64 = a.ws ? kPatch3Max64 : kPatchMax64;
-  if (a.tile == 4 || a.tile == 0) {
+  if (forced == T::T128x128 || automatic) {
     const long M = (long)(a.pick_B > 0 ? a.pick_B : a.B) * a.Hout * a.Wout;
     const long b128 = ((M + 127) / 128) * ((a.Cout + 127) / 128);
     const long b128x64 = ((M + 127) / 128) * ((a.Cout + 63) / 64);
-    if ((a.tile == 4 || (a.Cout >= 128 && b128 >= 512)) && conv_patch_geom(a, 128, g) && g.P <= max128)
-      return 4;
-    if (a.tile == 0 && b128x64 >= 512 && conv_patch_geom(a, 128, g) && g.P <= max128) return 5;
+    if ((!automatic || (a.Cout >= 128 && b128 >= 512)) && conv_patch_geom(a, 128, g) && g.P <= max128)
+      return T::T128x128;
+    if (automatic && b128x64 >= 512 && conv_patch_geom(a, 128, g) && g.P <= max128) return T::T128x64;
     // 64-pixel-wide maps (ADM 64^2): two whole rows per 128-row tile need the row-segment kernel's LDS image
     const int Wo = a.upsample == 2 ? a.Win : a.Wout;
-    if (a.tile == 0 && a.ws && a.ws_np == 2 && Wo >= 64 && conv_patch_geom(a, 128, g) && g.TB == 1 &&
+    if (automatic && a.ws && a.ws_np == 2 && Wo >= 64 && conv_patch_geom(a, 128, g) && g.TB == 1 &&
         g.P <= kPatch3Seg && g.P > max128)
-      return 9;
-    if (a.tile == 0 && conv_patch_geom(a, 64, g) && g.P <= max64) return 6;
-  } else if (a.tile == 5) {
-    if (conv_patch_geom(a, 128, g) && g.P <= max128) return 5;
-  } else if (a.tile == 6) {
-    if (conv_patch_geom(a, 64, g) && g.P <= max64) return 6;
+      return T::Seg128;
+    if (automatic && conv_patch_geom(a, 64, g) && g.P <= max64) return T::T64x64;
+  } else if (forced == T::T128x64) {
+    if (conv_patch_geom(a, 128, g) && g.P <= max128) return forced;
+  } else if (forced == T::T64x64) {
+    if (conv_patch_geom(a, 64, g) && g.P <= max64) return forced;
   }
-  return 0;
+  return T::None;
+}
+
+// the epilogues of Patch / Patch3 / Pointwise3 tiles whose waves own whole 64-row chunks: 64-pixel chunks of one
+// image, groups within 32 channels; not for the upsample forms
+bool conv_patch_can_emit(const ConvArgs& a) {
+  if (a.upsample) return false;
+  if ((a.Hout * a.Wout) % 64 != 0 || a.gn_G <= 0 || a.Cout % a.gn_G != 0) return false;
+  return 32 % (a.Cout / a.gn_G) == 0;
 }
 
 // Whether a conv can run on the split-bf16 kernel at every batch size: the 64-row tile (the
@@ -523,10 +545,10 @@ bool conv_seg_eligible(const ConvArgs& a) {
   return conv_patch_geom(a, 128, g) && g.TB == 1 && g.P <= kPatch3Seg;
 }
 
-int conv2d_patch(const ConvArgs& a, int which, const PatchGeom& g, hipStream_t st) {
-  switch (which) {
-    case 4: return launch_patch<128, 128, 64, 64, kPatchMax128>(a, g, st);
-    case 5: return launch_patch<128, 64, 64, 32, kPatchMax128>(a, g, st);
+int conv2d_patch(const ConvArgs& a, ConvTile tile, const PatchGeom& g, hipStream_t st) {
+  switch (tile) {
+    case ConvTile::T128x128: return launch_patch<128, 128, 64, 64, kPatchMax128>(a, g, st);
+    case ConvTile::T128x64: return launch_patch<128, 64, 64, 32, kPatchMax128>(a, g, st);
     default: return launch_patch<64, 64, 32, 32, kPatchMax64>(a, g, st);
   }
 }

@@ -634,12 +634,7 @@ int launch3(const ConvArgs& a, const PatchGeom& g, hipStream_t st) {
   const bool sub = a.upsample == 2;
   const int M = sub ? a.B * a.Hin * a.Win : a.B * a.Hout * a.Wout;
   const int ks = a.ksplit > 1 ? a.ksplit : 1;
-  DM_REQUIRE(ks == 1 || (!a.upsample && a.kpart && ks <= a.Cin1 / kSK),
-             "conv: split-K needs a stride-1 3x3 conv, a workspace and at most one split per channel chunk");
-  DM_REQUIRE(g.P <= MAXP, "conv: patch larger than the split kernel's LDS image");
-  DM_REQUIRE(NP == 3 || a.ws_rowscale, "conv: fp16x2 split weights need their row scales");
-  DM_REQUIRE((BM <= 128 && MAXP != kPatch3Seg) || (ks == 1 && a.stride == 1 && !(MAXP == kPatch3Seg && a.upsample == 1)),
-             "conv: the big / row-segment split tiles run stride-1 convs without split-K");
+  DM_REQUIRE(g.P <= MAXP, "conv: patch larger than the split kernel's LDS image");  // (conv_patch3_ok's bound)
   const int blocks = ceil_div(M, BM) * ceil_div(a.Cout, BN) * (sub ? 4 : 1) * ks;
   if (sub)
     launch3_mode<BM, BN, WM, WN, 2, MAXP, NP>(a, g, blocks, st);
@@ -736,19 +731,20 @@ extern "C" int dm_debug_pw_stamps(void* host, int nblocks) {
 }
 #endif
 
-bool conv_patch3_ok(const ConvArgs& a, int which, const PatchGeom& g) {
+bool conv_patch3_ok(const ConvArgs& a, ConvTile tile, const PatchGeom& g) {
+  using T = ConvTile;
   if (!a.ws || a.Cin1 % kSK != 0 || a.Cin2 % kSK != 0 || a.K % kSK != 0) return false;
-  if (a.stride == 2) return a.ws_np == 2 && which == 6 && g.P <= kPatchS2Max;  // MODE 4: fp16x2, 64-row tiles
-  if (which == 9) {  // 128-pixel row segments: fp16x2, one image's GroupNorm tables
+  if (a.stride == 2) return a.ws_np == 2 && tile == T::T64x64 && g.P <= kPatchS2Max;  // MODE 4: fp16x2, 64-row tiles
+  if (tile == T::Seg128) {  // 128-pixel row segments: fp16x2, one image's GroupNorm tables
     if (a.ws_np != 2 || (a.pro_scale && (long)g.TB * a.Cin1 * 2 > kSegTabFloats)) return false;
     return g.P <= kPatch3Seg;
   }
-  if (which == 7 || which == 8) {  // one wave per SIMD, 128 x 128 wave tiles: fp16x2 only
+  if (tile == T::T256x256 || tile == T::T512x128) {  // one wave per SIMD, 128 x 128 wave tiles: fp16x2 only
     if (a.ws_np != 2 || (a.pro_scale && (long)g.TB * a.Cin1 * 2 > kPwTabFloats)) return false;
-    return g.P <= (which == 7 ? kPatch3Max256 : kPatch3Max512);
+    return g.P <= (tile == T::T256x256 ? kPatch3Max256 : kPatch3Max512);
   }
   if (a.ws_np == 2 && a.pro_scale && (long)g.TB * a.Cin1 * 2 > kPwTabFloats) return false;  // LDS GroupNorm tables
-  return g.P <= (which == 6 ? kPatch3Max64 : kPatch3Max128);
+  return g.P <= (tile == T::T64x64 ? kPatch3Max64 : kPatch3Max128);
 }
 
 bool conv_pw_ok(const ConvArgs& a) {
@@ -760,45 +756,49 @@ bool conv_pw_ok(const ConvArgs& a) {
   return !a.pro_scale || (long)(127 / hw + 2) * a.Cin1 * 2 <= kPwTabFloats;
 }
 
-bool conv_lds_tables(const ConvArgs& a) {
-  if (!a.pro_scale || a.ws_np != 2) return false;
-  if (a.taps == 1) return conv_pw_ok(a);
-  if (a.taps != 9 || conv_pick(a) < 3) return false;
-  // a forced K32 tile (ConvArgs::tile 10 ..) gives conv_pick() >= 3 without a halo-patch geometry: not this path
-  // (g would be read unset, and the answer would be whatever the stack held)
-  PatchGeom g{};
-  if (!conv_patch_pick(a, g)) return false;
-  return conv_patch3_ok(a, conv_pick(a) + 1, g);
-}
-
-int conv2d_patch3(const ConvArgs& a, int which, const PatchGeom& g, hipStream_t st) {
+// what the launcher refuses of a Patch3 / Pointwise3 choice (its DM_REQUIREs; conv_choose reports them as the error)
+const char* conv_patch3_refuses(const ConvArgs& a, const ConvChoice& ch) {
+  using T = ConvTile;
   if (a.gin_part) {
     const long hw = (long)a.Hout * a.Wout;
-    const long imgs = a.taps == 1 ? 127 / hw + 2 : g.TB;
-    DM_REQUIRE(conv_lds_tables(a) && a.gin_G > 0 && a.Cin1 % a.gin_G == 0 && imgs * a.gin_G <= kGinStats,
-               "conv: in-kernel GroupNorm finalize needs the LDS-table path and <= 512 (image, group) pairs");
+    const long imgs = a.taps == 1 ? 127 / hw + 2 : ch.geom.TB;
+    if (!(ch.lds_tables && a.gin_G > 0 && a.Cin1 % a.gin_G == 0 && imgs * a.gin_G <= kGinStats))
+      return "conv: in-kernel GroupNorm finalize needs the LDS-table path and <= 512 (image, group) pairs";
   }
-  if (a.taps == 1) {
-    DM_REQUIRE(conv_pw_ok(a), "conv: the split 1x1 path needs fp16x2 weights, stride 1, K = Cin1 % 32 == 0 and LDS room for the GroupNorm tables");
-    return which == 4 ? launch_pw<128, 64>(a, st) : launch_pw<64, 32>(a, st);
-  }
-  if (a.stride == 2) {
-    DM_REQUIRE(a.ws_np == 2 && which == 6, "conv: the split stride-2 conv runs fp16x2 on 64-row tiles");
-    return launch3<64, 64, 32, 32, kPatchS2Max, 2>(a, g, st);
-  }
+  if (a.taps == 1)
+    return conv_pw_ok(a) ? nullptr
+                         : "conv: the split 1x1 path needs fp16x2 weights, stride 1, K = Cin1 % 32 == 0 and LDS room "
+                           "for the GroupNorm tables";
+  if (a.stride == 2 && !(a.ws_np == 2 && ch.tile == T::T64x64))
+    return "conv: the split stride-2 conv runs fp16x2 on 64-row tiles";
+  if (a.ksplit > 1 && !(!a.upsample && a.kpart && a.ksplit <= a.Cin1 / kSK))
+    return "conv: split-K needs a stride-1 3x3 conv, a workspace and at most one split per channel chunk";
+  if (a.ws_np == 2 && !a.ws_rowscale) return "conv: fp16x2 split weights need their row scales";
+  const bool big = a.ws_np == 2 && a.stride != 2 && (ch.tile == T::T256x256 || ch.tile == T::T512x128 || ch.tile == T::Seg128);
+  if (big && !(a.ksplit <= 1 && a.stride == 1 && !(ch.tile == T::Seg128 && a.upsample == 1)))
+    return "conv: the big / row-segment split tiles run stride-1 convs without split-K";
+  return nullptr;
+}
+
+int conv2d_patch3(const ConvArgs& a, const ConvChoice& ch, hipStream_t st) {
+  using T = ConvTile;
+  const PatchGeom& g = ch.geom;
+  if (const char* e = conv_patch3_refuses(a, ch)) DM_REQUIRE(false, e);
+  if (a.taps == 1) return ch.tile == T::T128x128 ? launch_pw<128, 64>(a, st) : launch_pw<64, 32>(a, st);
+  if (a.stride == 2) return launch3<64, 64, 32, 32, kPatchS2Max, 2>(a, g, st);
   if (a.ws_np == 2) {
-    switch (which) {
-      case 9: return launch3<128, 128, 64, 64, kPatch3Seg, 2>(a, g, st);
-      case 7: return launch3<256, 256, 128, 128, kPatch3Max256, 2>(a, g, st);
-      case 8: return launch3<512, 128, 128, 128, kPatch3Max512, 2>(a, g, st);
-      case 4: return launch3<128, 128, 64, 64, kPatch3Max128, 2>(a, g, st);
-      case 5: return launch3<128, 64, 64, 32, kPatch3Max128, 2>(a, g, st);
+    switch (ch.tile) {
+      case T::Seg128: return launch3<128, 128, 64, 64, kPatch3Seg, 2>(a, g, st);
+      case T::T256x256: return launch3<256, 256, 128, 128, kPatch3Max256, 2>(a, g, st);
+      case T::T512x128: return launch3<512, 128, 128, 128, kPatch3Max512, 2>(a, g, st);
+      case T::T128x128: return launch3<128, 128, 64, 64, kPatch3Max128, 2>(a, g, st);
+      case T::T128x64: return launch3<128, 64, 64, 32, kPatch3Max128, 2>(a, g, st);
       default: return launch3<64, 64, 32, 32, kPatch3Max64, 2>(a, g, st);
     }
   }
-  switch (which) {
-    case 4: return launch3<128, 128, 64, 64, kPatch3Max128, 3>(a, g, st);
-    case 5: return launch3<128, 64, 64, 32, kPatch3Max128, 3>(a, g, st);
+  switch (ch.tile) {
+    case T::T128x128: return launch3<128, 128, 64, 64, kPatch3Max128, 3>(a, g, st);
+    case T::T128x64: return launch3<128, 64, 64, 32, kPatch3Max128, 3>(a, g, st);
     default: return launch3<64, 64, 32, 32, kPatch3Max64, 3>(a, g, st);
   }
 }

@@ -951,6 +951,12 @@ bool conv_wino_ok(const ConvArgs& a) {
   return a.wino_ws && a.wino_rowscale && conv_wino_shape_ok(a) && (a.Cin2 == 0 || a.wino_fold == (int)wino_fold_of(a));
 }
 
+// StagedEpilogue over 64-pixel chunks of one image: groups of 4 .. 32 channels (the 4 x 4 maps' statistics come from
+// the split-K reduction: conv_splitk_can_emit)
+bool conv_wino_can_emit(const ConvArgs& a) {
+  return a.gn_G > 0 && a.Cout % a.gn_G == 0 && (a.Cout / a.gn_G) % 4 == 0 && a.Cout / a.gn_G <= 32;
+}
+
 size_t wino_weights_bytes(int Cout, int Cin1, int Cin2) { return split_conv_weights_bytes(4, Cout, 3 * Cin1 + Cin2 / 2, 2); }
 
 const float* wino_rowscale(const void* ws, int Cout, int Cin1, int Cin2) {

@@ -20,10 +20,10 @@ struct Toggles {
   bool wino = true;           // DM_CONV_WINO=0: the 3x3 convs of 32^2 / 16^2 maps on conv_k32 instead of conv_wino
   bool subwino = true;        // DM_CONV_SUBWINO=0: the Upsample convs of 4^2 / 8^2 / 16-wide low-res maps as four
                               // sub-pixel convs (conv_k32, conv_patch3 MODE 2) instead of conv_subwino
-  bool k32s_w4 = false;       // DM_K32S_W4=1: the small-map conv's 4-wave form (conv_k32 variant 12)
-  bool k32_small = true;      // DM_CONV_K32S=0: split-K convs of <= 16-pixel maps as two launches (conv_k32 3 / 4)
-  bool k32_s2 = true;         // DM_CONV_K32S2=0: stride-2 convs on conv_patch3 MODE 4 instead of conv_k32 variant 9
-  bool k32_t2d = true;        // DM_CONV_K32T2=0: wide maps on 128-pixel row segments (variant 7), not 2-D tiles
+  bool k32s_w4 = false;       // DM_K32S_W4=1: the small-map conv's 4-wave form (K32Form::Small4)
+  bool k32_small = true;      // DM_CONV_K32S=0: split-K convs of <= 16-pixel maps as two launches (K32Form::SplitK*)
+  bool k32_s2 = true;         // DM_CONV_K32S2=0: stride-2 convs on conv_patch3 MODE 4 instead of K32Form::S2 / S2Seg
+  bool k32_t2d = true;        // DM_CONV_K32T2=0: wide maps on 128-pixel row segments (K32Form::Wide512), not T2D tiles
   bool k32_8x = true;         // DM_K32_8X=0: 8^2 maps on 128 x 128 two-image tiles instead of 64-row tiles
   bool gn_fusion = true;      // DM_GN_FUSION=0: GroupNorm statistics by separate passes (no producer epilogues,
                               // no concat units, no first-conv statistics)
@@ -85,7 +85,7 @@ struct ConvArgs {
   int rowvec_pitch;
   const float* res;     // residual at output resolution or null
   int res_pitch;
-  int tile;      // 0 auto; 1..3 force an im2col tile, 4..6 a halo-patch tile
+  int tile;      // 0 automatic; 1..23 force one kernel form (tests, tuning): the table in conv.hip, DESIGN.md §4.21
   int pick_B;           // batch the tile heuristics assume (0: B). Plans pass a fixed one, so a layer's
                         // kernel (and its summation order) never changes with B: batch-invariant results
   // optional operand prologue on segment 1 (halo-patch kernel only):
@@ -96,7 +96,7 @@ struct ConvArgs {
   int pro_nosilu;  // 1: the prologue is the affine alone (no SiLU)
   // optional: the kernel computes its GroupNorm prologue tables itself from gn_partial-layout statistics
   // of x1 ([B][gin_nchunk][gin_G] {sum, sumsq}), exactly as gn_finalize would (same expressions), into
-  // LDS; the finalize launch is skipped. Only where conv_lds_tables() holds.
+  // LDS; the finalize launch is skipped. Only where ConvChoice::lds_tables holds.
   const double2* gin_part;
   int gin_G, gin_nchunk;
   double gin_n;
@@ -137,9 +137,6 @@ struct ConvArgs {
   const void* wino_ws;
   const float* wino_rowscale;
   int wino_fold;  // the shortcut segment's weights were packed with the SiLU fold (wino_weights fold = 1)
-  // the K32 variant the plan resolved at build time (conv_k32_pick + 1; 0: pick at launch), so the launch and the
-  // op's profile label come from one decision
-  int k32_resolved;
   int s2_pad0;  // 1: stride-2 taps start at 2o (input padded bottom/right only); 0: at 2o - 1 (padding 1)
   // the conv-half option of the UNet plans (conv_h16.hip): h16 = 1 marks a conv conv_h16_ok takes in
   // a plan with the switch on (ExecNet::split_for); such a conv runs conv_h16_image (prologue, one rounding to fp16:
@@ -325,47 +322,75 @@ int unpatchify(const float* x, int B, int C, int H, int W, int p, float* out, hi
 int gn_apply(const View& x, int G, const double2* part, int nchunk, float eps, const float* gamma,
              const float* beta, const float* mod_scale, const float* mod_shift, int mod_pitch, int act,
              const View& y, hipStream_t st);
-int conv2d_igemm(const ConvArgs& a, hipStream_t st);
-int conv_pick(const ConvArgs& a);
-// whether the conv can emit GroupNorm(gn_G) statistics of its output from the epilogue
-bool conv_can_emit_gn(const ConvArgs& a);
+// The conv decision (conv.hip; the families, their forms and the public tile numbers: DESIGN.md §4.21). conv_choose
+// decides once which kernel runs a ConvArgs; the launch, the profile label and every question a plan asks read that
+// one ConvChoice. The per-family gates (conv_*_ok) and statistics rules (conv_*_can_emit) sit next to their launchers.
+enum class ConvFamily { Im2col, Patch, Patch3, Pointwise3, K32, K32Small, Wino, SubWino, H16 };
+// BM x BN of an Im2col / Patch / Patch3 / Pointwise3 tile (Seg128: Patch3's 128-pixel row segments of wide maps)
+enum class ConvTile { None, T128x128, T128x64, T64x64, T256x256, T512x128, Seg128 };
+// conv_k32.hip's forms, in the order of its label table (K32Small: Small8 and its 4-wave form Small4)
+enum class K32Form { None, T128x128, T128x64, SplitK64x64, SplitK64x128, Seg64, Small8, Wide512, BigTab, S2, T2D,
+                     Rows64, Small4, S2Seg };
+enum class H16Form { None, Rows, T2D };
+struct ConvChoice {
+  ConvFamily family = ConvFamily::Im2col;
+  ConvTile tile = ConvTile::None;  // Im2col, Patch, Patch3, Pointwise3
+  K32Form k32 = K32Form::None;     // K32, K32Small
+  H16Form h16 = H16Form::None;     // H16
+  PatchGeom geom{};  // the conv's halo-patch tiling (conv_patch_pick; zero where none): Patch / Patch3 launch on it, and
+                     // geom.TB bounds the images per tile of the plans' in-kernel GroupNorm finalize
+  bool emits_gn = false;        // this kernel, on this ConvArgs (gn_part, gn_G set), can write gn_part
+  bool takes_prologue = false;  // a halo-patch / split 1x1 shape: pro_scale / pro_shift are applied on load
+  bool lds_tables = false;      // ... from tables staged in LDS, so the conv can take ConvArgs::gin_* instead
+  const char* error = nullptr;  // non-null: the conv is refused (DM_ERR_ARG) with this text
+  bool k32_stride2() const { return k32 == K32Form::S2 || k32 == K32Form::S2Seg; }  // conv_k32 runs this stride-2 conv
+};
+ConvChoice conv_choose(const ConvArgs& a);
+int conv2d_run(const ConvArgs& a, const ConvChoice& ch, hipStream_t st);
+inline int conv2d_igemm(const ConvArgs& a, hipStream_t st) { return conv2d_run(a, conv_choose(a), st); }
+// rocprofv3's name of the instantiation the choice launches (spaces removed); "family:variant" for the tests
+std::string conv_label(const ConvArgs& a, const ConvChoice& ch);
+inline std::string conv_label(const ConvArgs& a) { return conv_label(a, conv_choose(a)); }
+std::string conv_choice_name(const ConvArgs& a, const ConvChoice& ch);
+inline bool conv_can_emit_gn(const ConvArgs& a) { return conv_choose(a).emits_gn; }  // (asked with gn_part set)
+// a non-null, 16-byte aligned address for a pointer of a ConvArgs asked about before the buffer exists (never read)
+template <class T>
+inline T* conv_standin() { return reinterpret_cast<T*>(16); }
+// halo-patch tiles (conv_patch.hip): a BM-row tile's geometry, the tile a conv takes (forced: that tile or none;
+// None: the automatic choice), what the launchers refuse, the statistics rules of the 64-row-chunk epilogues
+// (Patch, Patch3, Pointwise3) and of the split-K reduction
 bool conv_patch_geom(const ConvArgs& a, int BM, PatchGeom& g);
-int conv_patch_pick(const ConvArgs& a, PatchGeom& g);
-int conv2d_patch(const ConvArgs& a, int which, const PatchGeom& g, hipStream_t st);
-// split-bf16 halo-patch kernel (conv_patch3.hip): whether it takes this shape / tile, and its launcher
-bool conv_patch3_ok(const ConvArgs& a, int which, const PatchGeom& g);
-// 1x1 convs / static-weight GEMMs on the fp16x2 split kernel (conv_patch3_kernel MODE 3)
+ConvTile conv_patch_pick(const ConvArgs& a, ConvTile forced, PatchGeom& g);
+const char* conv_patch_refuses(const ConvArgs& a);
+int conv2d_patch(const ConvArgs& a, ConvTile tile, const PatchGeom& g, hipStream_t st);
+bool conv_patch_can_emit(const ConvArgs& a);
+bool conv_splitk_can_emit(const ConvArgs& a);
+// the split halo-patch kernel (conv_patch3.hip; Pointwise3: its 1x1 / static-weight GEMM mode, conv_pw_ok)
+bool conv_patch3_ok(const ConvArgs& a, ConvTile tile, const PatchGeom& g);
+const char* conv_patch3_refuses(const ConvArgs& a, const ConvChoice& ch);
 bool conv_pw_ok(const ConvArgs& a);
-// whether the conv stages its GroupNorm prologue tables in LDS (and so can take ConvArgs::gin_* instead
-// of finalized tables)
-bool conv_lds_tables(const ConvArgs& a);
 bool conv_split_eligible(const ConvArgs& a);
 bool conv_seg_eligible(const ConvArgs& a);
-int conv2d_patch3(const ConvArgs& a, int which, const PatchGeom& g, hipStream_t st);
-// fp16x2 split conv with K = 32 steps on v_mfma_f32_16x16x32_f16 (conv_k32.hip): 3x3 stride-1 MODE 0
-// shapes. conv_k32_pick -> variant 1 (128 x 128 tiles), 2 (128 x 64), 3 (64 x 64 split-K), 4 (64 x 128
-// split-K) or 0 (not this kernel); forced by ConvArgs::tile 10..13, else it replaces conv_patch3's
-// 128-row and split-K tiles unless DM_CONV_K32=0)
-bool conv_k32_ok(const ConvArgs& a);
-int conv_k32_variant_ok(const ConvArgs& a, int v);
-int conv_k32_pick(const ConvArgs& a);
-int conv2d_k32(const ConvArgs& a, int v, hipStream_t st);
-std::string conv_k32_label(const ConvArgs& a, int v);
-// Winograd F(2,3)-along-x 3x3 convs (conv_wino.hip): the shapes the kernel takes (32- / 16-wide maps, 128-pixel
-// tiles, Cout % 128 == 0, a ResBlock shortcut segment of Cin2 % 64 == 0), whether a conv has its weights and shape, the
-// weights (U = G g, float64, then the fp16x2 split of split_conv_weights with nmat 4, ntap 3; fold: the shortcut's
-// weights times -log2(e), for convs whose prologue has the SiLU), their size / row scales, launcher
+int conv2d_patch3(const ConvArgs& a, const ConvChoice& ch, hipStream_t st);
+// conv_k32.hip: the gate of one form, the automatic choice (halo: conv_patch_pick's tile), a form's statistics rule
+// (rows64: the conv's halo-patch tile gives every wave whole 64-row chunks)
+bool conv_k32_variant_ok(const ConvArgs& a, K32Form v);
+K32Form k32_choose(const ConvArgs& a, ConvTile halo);
+bool conv_k32_can_emit(const ConvArgs& a, K32Form v, bool rows64);
+int conv2d_k32(const ConvArgs& a, K32Form v, hipStream_t st);
+std::string conv_k32_label(const ConvArgs& a, K32Form v);
+// conv_wino.hip: shape gate, gate with weights, the weights (U = G g in float64, then split_conv_weights with nmat 4,
+// ntap 3; fold: the shortcut's weights times -log2(e), for convs whose prologue has the SiLU), their size / row scales
 bool conv_wino_shape_ok(const ConvArgs& a);
 bool conv_wino_ok(const ConvArgs& a);
 size_t wino_weights_bytes(int Cout, int Cin1, int Cin2);
 const float* wino_rowscale(const void* ws, int Cout, int Cin1, int Cin2);
 int wino_weights(const float* w, int Cout, int Cin1, int Cin2, int fold, void* out, hipStream_t st);
+bool conv_wino_can_emit(const ConvArgs& a);
 std::string conv_wino_label(const ConvArgs& a);
 int conv2d_wino(const ConvArgs& a, hipStream_t st);
-// Sub-pixel Winograd upsample convs (conv_subwino.hip): the sub-pixel form (upsample = 2) of a nearest-2x + 3x3 conv
-// on 16-wide (rows % 4 == 0), 8 x 8 and 4 x 4 low-res maps, Cin % 32 == 0, Cout % 128 == 0, bias-only epilogue, no
-// prologue. subwino_pack: the six U matrices [6][Cout][2 Cin] in fp32 from the torch weight [Cout][Cin][3][3]
-// (float64 sums, one rounding); subwino_weights: that and their fp16x2 split (split_conv_weights, nmat 6, ntap 2).
+// conv_subwino.hip: subwino_pack: the six U matrices [6][Cout][2 Cin] in fp32 from the torch weight [Cout][Cin][3][3]
+// (float64 sums, one rounding); subwino_weights: that and their fp16x2 split (split_conv_weights, nmat 6, ntap 2)
 bool conv_subwino_shape_ok(const ConvArgs& a);
 bool conv_subwino_ok(const ConvArgs& a);
 size_t subwino_weights_bytes(int Cout, int Cin);
@@ -391,20 +416,15 @@ int linear_h16(const GemmArgs& g, hipStream_t st);
 int linear_h16_image(const GemmArgs& g, _Float16* out, hipStream_t st);
 int linear_h16_image_cat(const float* x, const float* skip, long M, int D, int ea, _Float16* out, int* range_flag,
                          hipStream_t st);
-// The conv-half option (conv_h16.hip): 3x3 stride-1 convs with ONE v_mfma_f32_16x16x32_f16 product per MAC on
-// a' = fp16_rne(prologue(x1)), a2' = fp16_rne(x2) and piece 0 of the fp16x2 fragment image in `ws`, fp32 accumulation,
-// the fp32 epilogue of conv_k32. conv_h16_ok is the single gate (shape, alignment, the staged epilogue's rules; the
-// planes, where set, 16-byte aligned); conv_h16_form the tile form a conv runs in (1: 128 x 128 tiles of whole rows
-// of 8- / 16- / 32-wide maps, two 8 x 8 images per tile; 2: 4 x 32-pixel 2-D tiles of 64- .. 256-wide maps; 0: none;
-// ConvArgs::tile 0 picks, 1 / 2 force). conv_h16_image writes the plane(s) and raises range_flag beyond 65504;
-// conv2d_h16 launches the kernel on ConvArgs::h16_a1 / h16_a2. conv_h16_can_emit: the GroupNorm partials rule of its
-// StagedEpilogue (conv_can_emit_gn answers with it for a conv marked h16).
+// The conv-half option (conv_h16.hip): conv_h16_ok is the single gate, conv_h16_form the tile form
+// (ConvArgs::tile 0 picks, 1 / 2 force Rows / T2D); conv_h16_image writes the fp16 plane(s) and raises range_flag beyond
+// 65504; conv2d_h16 launches on ConvArgs::h16_a1 / h16_a2; conv_h16_can_emit: its StagedEpilogue's statistics rule.
 bool conv_h16_ok(const ConvArgs& a);
-int conv_h16_form(const ConvArgs& a);
+H16Form conv_h16_form(const ConvArgs& a);
 bool conv_h16_can_emit(const ConvArgs& a);
 int conv_h16_image(const ConvArgs& a, _Float16* plane1, _Float16* plane2, hipStream_t st);
 int conv2d_h16(const ConvArgs& a, hipStream_t st);
-std::string conv_h16_label(const ConvArgs& a);
+std::string conv_h16_label(const ConvArgs& a, H16Form form);
 int conv_splitk_reduce(const ConvArgs& a, hipStream_t st);
 // fp32 packed conv weights [nmat][rows][K] -> split slices for conv_patch3_kernel (np 3: bf16x3,
 // np 2: fp16x2 + row scales); split_conv_rowscale gives ConvArgs::ws_rowscale of an fp16x2 copy
@@ -412,7 +432,6 @@ size_t split_conv_weights_bytes(int nmat, int rows, int K, int np);
 const float* split_conv_rowscale(const void* ws, int nmat, int rows, int K);
 int split_conv_weights(const float* w, int nmat, int rows, int K, int cin1, int ntap, int np, void* out,
                        hipStream_t st);
-std::string conv_label(const ConvArgs& a);
 // DM_CONV_MATH: fp16x2 (default) -> 2, bf16x3 -> 3, fp32 -> 0 (ConvArgs::ws_np of the model's convs), from the
 // plan's toggle snapshot
 inline int conv_math_from_env() { return toggles().conv_math; }

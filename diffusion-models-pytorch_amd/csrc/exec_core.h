@@ -110,11 +110,10 @@ struct ExecNet {
     bool s2seg = false;
     if (conv_math == 2 && c.s2_pad0 && c.stride == 2 && c.taps == 9) {
       ConvArgs t = c;
-      t.ws = reinterpret_cast<const void*>(16);  // placeholders: the shape checks only
+      t.ws = conv_standin<const void>();
       t.ws_np = 2;
-      t.ws_rowscale = reinterpret_cast<const float*>(16);
-      const int v = conv_k32_pick(t);
-      s2seg = v == 9 || v == 13;
+      t.ws_rowscale = conv_standin<const float>();
+      s2seg = conv_choose(t).k32_stride2();
     }
     if (!conv_math || !(conv_split_eligible(c) || (conv_math == 2 && conv_seg_eligible(c)) || s2seg)) return;
     if ((c.taps == 1 || c.stride == 2) && conv_math != 2) return;  // the split 1x1 / stride-2 paths are fp16x2 only

@@ -713,11 +713,11 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     if (conv_math == 2 && toggles().wino && wino_small_ks(c)) {
       ConvArgs w = c;
       w.ksplit = wino_small_ks(c);
-      w.kpart = reinterpret_cast<float*>(16);  // placeholder: the shape check only
+      w.kpart = conv_standin<float>();
       if (conv_wino_shape_ok(w)) ks = w.ksplit;
     }
     if (!ks) {
-      if (conv_pick(c) < 3) return;
+      if (!conv_choose(c).takes_prologue) return;
       ks = std::min(2, c.Cin1 / 32);
       if (ks < 2) return;
     }
@@ -740,7 +740,6 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       }
       c.h16_a1 = h16_p1;
       c.h16_a2 = c.Cin2 ? h16_p2 : nullptr;
-      c.k32_resolved = 0;
       double fl, by;
       conv_cost(c, fl, by);
       const double npix = (double)c.B * c.Hin * c.Win;
@@ -750,10 +749,10 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       add(conv_label(c), fl, by - 2.0 * npix * (c.Cin1 + c.Cin2), [=](hipStream_t st) { return conv2d_h16(c, st); });
       return;
     }
-    c.k32_resolved = 1 + conv_k32_pick(c);  // one decision for the launch and the label
+    const ConvChoice ch = conv_choose(c);  // one decision for the launch and the label
     double fl, by;
     conv_cost(c, fl, by);
-    add(conv_label(c), fl, by, [=](hipStream_t st) { return conv2d_igemm(c, st); });
+    add(conv_label(c, ch), fl, by, [=](hipStream_t st) { return conv2d_run(c, ch, st); });
   };
   auto add_gemm = [&](const GemmArgs& g) {
     double fl, by;
@@ -851,7 +850,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     gn_ready.erase(v.p);
     for (const int Gv : {emit_groups(v), G}) {
       ConvArgs sk = c;
-      sk.gn_part = reinterpret_cast<double2*>(16);  // placeholder: the shape check only
+      sk.gn_part = conv_standin<double2>();
       sk.gn_G = Gv;
       maybe_split(sk);  // split-K is shape-determined; its reduction emits the statistics
       split_for(sk);    // the kernel add_conv will launch (Winograd or direct: their statistics rules differ)
@@ -896,20 +895,17 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
     return gn_stats(v);
   };
   // GroupNorm(G) of v feeding conv c's prologue (tables gsc / gsh): either the conv finalizes the
-  // statistics itself into its LDS tables (conv_lds_tables: no gn_finalize launch) or gn_finalize runs.
+  // statistics itself into its LDS tables (ConvChoice::lds_tables: no gn_finalize launch) or gn_finalize runs.
   auto gn_prologue = [&](ConvArgs& c, const View& v, const double2* stp, size_t gamma, size_t beta,
                          const float* ms, const float* mb, int mp) {
     c.pro_scale = gsc;
     c.pro_shift = gsh;
     split_for(c);
-    const long imgs = c.taps == 1 ? 127 / ((long)c.Hout * c.Wout) + 2 : [&] {
-      PatchGeom gg;
-      conv_patch_pick(c, gg);
-      return (long)gg.TB;
-    }();
+    const ConvChoice ch = conv_choose(c);
+    const long imgs = c.taps == 1 ? 127 / ((long)c.Hout * c.Wout) + 2 : (long)ch.geom.TB;
     // in-kernel finalize: every block re-reduces its images' chunk partials, so only for small maps
     // (CIFAR: <= 16 chunks per image); the 256^2 maps of ADM have 1024 and take the finalize launch
-    if (!c.h16 && conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
+    if (!c.h16 && ch.lds_tables && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
       c.gin_part = stp; c.gin_G = G; c.gin_nchunk = gn_num_chunks(v.H * v.W);
       c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = gn_eps;
       c.gin_gamma = P(gamma); c.gin_beta = P(beta); c.gin_ms = ms; c.gin_mb = mb; c.gin_mp = mp;
@@ -978,7 +974,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         ConvArgs s = c;
         s.upsample = 2; s.w = P(w_sub); s.K = 4 * c.Cin1;
         split_for(s);  // the tile choice depends on the split copy (fp16x2-only tiles)
-        if (conv_pick(s) >= 3) c = s;
+        if (conv_choose(s).takes_prologue) c = s;
       };
       ConvArgs c2{};
       c2.x1 = a2; c2.x1_pitch = r.cout; c2.Cin1 = r.cout; c2.Hin = Ho; c2.Win = Wo;
@@ -994,7 +990,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
       split_for(c1);
       split_for(c2);
       try_subpix(c1, r.conv1.w_sub);
-      const bool fuse1 = r.updown != 2 && conv_pick(c1) >= 3, fuse2 = conv_pick(c2) >= 3;
+      const bool fuse1 = r.updown != 2 && conv_choose(c1).takes_prologue, fuse2 = conv_choose(c2).takes_prologue;
       // AdaGN modulation gn(h) * (1 + ys) + yb, [ys | yb] from the fused projection (modules.py:114-123)
       const float* ms = r.adagn ? projs + r.proj_col : nullptr;
       const float* mb = r.adagn ? projs + r.proj_col + r.cout : nullptr;
@@ -1269,7 +1265,7 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         ConvArgs s = c;
         s.upsample = 2; s.w = P(cv.w_sub); s.K = 4 * c.Cin1;
         split_for(s);
-        if (conv_pick(s) >= 3) c = s;
+        if (conv_choose(s).takes_prologue) c = s;
         // whole-row low-res maps of 4 / 8 / 16 columns: the sub-pixel Winograd kernel (3/4 of the MFMA products)
         if (c.upsample == 2 && cv.has_subw) subwino_for(c, P(cv.w_subw));
       }
@@ -1281,8 +1277,8 @@ int UNetModel::build_plan(Plan& pl, int B, int H, int W) {
         // plan never takes otherwise (reference-fixture forwards off by 0.14)
         ConvArgs s = c;
         split_for(s);
-        const int v = conv_k32_pick(s);
-        if (v == 9 || (c.s2_pad0 && v == 13)) {  // (13: the row-segment form of the bottom/right-padded conv)
+        const K32Form v = conv_choose(s).k32;
+        if (v == K32Form::S2 || (c.s2_pad0 && v == K32Form::S2Seg)) {  // (the row-segment form: bottom/right-padded only)
           c = s;
           emit_conv(c, y);
         } else {

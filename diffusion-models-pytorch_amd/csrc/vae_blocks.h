@@ -160,10 +160,10 @@ struct BlockPlanner {
   }
   void add_conv(ConvArgs c) {
     net->split_for(c);
-    c.k32_resolved = 1 + conv_k32_pick(c);
+    const ConvChoice ch = conv_choose(c);  // one decision for the launch and the label
     double fl, by;
     conv_cost(c, fl, by);
-    add(conv_label(c), fl, by, [c](hipStream_t st) { return conv2d_igemm(c, st); });
+    add(conv_label(c, ch), fl, by, [c, ch](hipStream_t st) { return conv2d_run(c, ch, st); });
   }
   void add_gemm(const GemmArgs& g) {
     double fl, by;
@@ -178,7 +178,7 @@ struct BlockPlanner {
     c.gn_G = 0;
     if (!toggles().gn_fusion) return;
     ConvArgs sk = c;
-    sk.gn_part = reinterpret_cast<double2*>(16);  // placeholder: the shape check only
+    sk.gn_part = conv_standin<double2>();
     sk.gn_G = G;
     net->split_for(sk);
     if (!conv_can_emit_gn(sk)) return;
@@ -204,14 +204,11 @@ struct BlockPlanner {
     c.pro_scale = gsc;
     c.pro_shift = gsh;
     net->split_for(c);
-    const long imgs = c.taps == 1 ? 127 / ((long)c.Hout * c.Wout) + 2 : [&] {
-      PatchGeom gg{};
-      conv_patch_pick(c, gg);
-      return (long)gg.TB;
-    }();
+    const ConvChoice ch = conv_choose(c);
+    const long imgs = c.taps == 1 ? 127 / ((long)c.Hout * c.Wout) + 2 : (long)ch.geom.TB;
     const float* gamma = net->P(gw.g);
     const float* beta = net->P(gw.b);
-    if (conv_lds_tables(c) && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
+    if (ch.lds_tables && imgs * G <= 512 && v.C == c.Cin1 && gn_num_chunks(v.H * v.W) <= 64) {
       c.gin_part = stp; c.gin_G = G; c.gin_nchunk = gn_num_chunks(v.H * v.W);
       c.gin_n = (double)v.H * v.W * (v.C / G); c.gin_eps = eps;
       c.gin_gamma = gamma; c.gin_beta = beta; c.gin_ms = nullptr; c.gin_mb = nullptr; c.gin_mp = 0;
@@ -257,7 +254,7 @@ struct BlockPlanner {
     }
     net->split_for(c1);
     net->split_for(c2);
-    const bool fuse1 = conv_pick(c1) >= 3, fuse2 = conv_pick(c2) >= 3;
+    const bool fuse1 = conv_choose(c1).takes_prologue, fuse2 = conv_choose(c2).takes_prologue;
     const double2* st1 = gn_stats(xin);
     const GnW g1 = r.gn1, g2 = r.gn2;
     const int G_ = G;

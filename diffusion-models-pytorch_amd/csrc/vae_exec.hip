@@ -294,7 +294,7 @@ int VaeDecoder::build_plan(Plan& pl, int B, int H, int W) {
       ConvArgs s = c;
       s.upsample = 2; s.w = P(cv.w_sub); s.K = 4 * c.Cin1;
       split_for(s);
-      if (conv_pick(s) >= 3) c = s;
+      if (conv_choose(s).takes_prologue) c = s;
     }
     if (c.upsample == 2)
       bp.emit_conv(c, y);

@@ -274,6 +274,9 @@ def _declare(L: ctypes.CDLL):
     L.dm_conv2d_nhwc.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.dm_conv2d_nhwc_s2pad0.argtypes = [ctypes.POINTER(ConvDesc), vp]
     L.dm_debug_conv2d_gn.argtypes = [ctypes.POINTER(ConvDesc), ctypes.c_int, ctypes.c_int, vp, vp]
+    L.dm_debug_conv_choice.argtypes = [ctypes.POINTER(ConvDesc)] + [ctypes.c_int] * 8 + [
+        ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_char_p,
+        ctypes.c_int]
     L.dm_pack_conv_weight_subpixel.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp]
     L.dm_debug_launch_log.argtypes = [ctypes.c_int]
     L.dm_debug_launch_log_read.argtypes = [ctypes.c_char_p, ctypes.c_int]
@@ -668,6 +671,19 @@ def conv2d_gn_stats(desc: ConvDesc, G: int, part: torch.Tensor, s2_pad0: bool = 
     require_device_tensor(part, 'part', torch.float64)
     check(load().dm_debug_conv2d_gn(ctypes.byref(desc), int(bool(s2_pad0)), G, part.data_ptr(), stream_handle(device)),
           'dm_debug_conv2d_gn')
+
+
+def conv_choice(desc: ConvDesc, s2_pad0=0, gn_G=0, gn_emit=0, pick_B=0, ksplit_has_part=0, h16=0, gin_G=0,
+                gin_nchunk=0) -> dict:
+    """dm_debug_conv_choice: the kernel the conv of `desc` would run, decided on the host (no GPU, no tensor read):
+    {'label', 'emits_gn', 'lds_tables', 'launched'}; launched is 'family:variant', or 'refused' for an error."""
+    label, launched = ctypes.create_string_buffer(160), ctypes.create_string_buffer(64)
+    emits, lds = ctypes.c_int(), ctypes.c_int()
+    check(load().dm_debug_conv_choice(ctypes.byref(desc), s2_pad0, gn_G, gn_emit, pick_B, ksplit_has_part, h16, gin_G,
+                                      gin_nchunk, label, len(label), ctypes.byref(emits), ctypes.byref(lds), launched,
+                                      len(launched)), 'dm_debug_conv_choice')
+    return {'label': label.value.decode(), 'emits_gn': emits.value, 'lds_tables': lds.value,
+            'launched': launched.value.decode()}
 
 
 def gemm(desc: GemmDesc, device=None):

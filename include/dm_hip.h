@@ -540,8 +540,9 @@ typedef struct dm_conv_desc {
   const float* bias;
   const float* rowvec; int rowvec_pitch;
   const float* res; int res_pitch;
-  int tile;  /* 0: automatic; 1..3 force the im2col kernel with a 128x128 / 128x64 / 64x64 tile,
-                4..6 the halo-patch kernel with those tiles (tests, tuning) */
+  int tile;  /* 0: automatic; 1..23 force one kernel form (tests, tuning): the table in DESIGN.md section 4.21
+                (kTileForms in csrc/conv.hip). A form that does not fit the conv falls back to the im2col kernel,
+                except 21 and 23 (the Winograd kernels), which fail then */
   /* optional fused GroupNorm+SiLU of the input: x -> silu(x * pro_scale[b][c] + pro_shift[b][c]),
    * [B][Cin] tables from dm_groupnorm_affine(); halo-patch shapes only (3x3 stride 1 / upsample) */
   const float* pro_scale;
@@ -575,6 +576,18 @@ int dm_conv2d_nhwc(const dm_conv_desc* d, void* stream);
  * stride == 2 and upsample == 0. tile as above; 18 forces the K = 32 split kernel's whole-row stride-2 tiles
  * (Wout <= 64), 22 its 64-pixel row segments (Wout > 64, Wout % 64 == 0), which tile 0 takes for this form only. */
 int dm_conv2d_nhwc_s2pad0(const dm_conv_desc* d, void* stream);
+/* Test hook, host only (no HIP call, no tensor is read, so stand-in addresses of the right alignment do): which
+ * kernel the conv of `d` would run. Beside the descriptor it takes what the model plans set on a conv: s2_pad0 as
+ * above; gn_G the GroupNorm group count of the output's consumer and gn_emit whether the conv is asked to emit its
+ * statistics; pick_B the nominal batch of the tile heuristics (0: B); ksplit_has_part: a split-K workspace is present
+ * even where d->kpart is NULL; h16: the conv-half mark; gin_G > 0: the prologue's GroupNorm is finalized in the
+ * kernel from gin_nchunk chunk partials (d->pro_scale NULL). Out: `label` the kernel instantiation as profiles name
+ * it; *emits_gn whether the kernel can emit GroupNorm(gn_G) statistics; *lds_tables whether it stages its GroupNorm
+ * tables in LDS; `launched` the decision as "family:variant" (DESIGN.md section 4.21), or "refused"
+ * where the conv is an error (label empty, both flags 0). Returns DM_ERR_ARG for a NULL argument only. */
+int dm_debug_conv_choice(const dm_conv_desc* d, int s2_pad0, int gn_G, int gn_emit, int pick_B, int ksplit_has_part,
+                         int h16, int gin_G, int gin_nchunk, char* label, int label_len, int* emits_gn,
+                         int* lds_tables, char* launched, int launched_len);
 
 typedef struct dm_gemm_desc {
   int M, N, K, Z1, Z2;

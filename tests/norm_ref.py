@@ -823,13 +823,13 @@ def gemm_case(s):
 
 
 # e. the convs' in-kernel GroupNorm finalize (ConvArgs::gin_* through dm_debug_conv2d_gin), one case per kernel
-# family for which conv_lds_tables() holds; B = 3, GroupNorm(32) of the input.
+# family for which ConvChoice::lds_tables holds; B = 3, GroupNorm(32) of the input.
 CONV_GIN_CASES = [
     # the 8^2 map on the two-image 128 x 128 tile, the 16^2 map on a two-images-per-block (512-row) tile, the 1x1
     _cv('patch3_8x8_two_images', 'conv_patch3_kernel<128,128,64,64,0,208,true', (), 3, 64, 64, 8, 8, 4),
     _cv('patch3_512_16x16_two_images', 'conv_patch3_kernel<512,128,128,128,0,656,true', (), 3, 64, 64, 16, 16, 8),
     _cv('pw_1x1', 'conv_patch3_kernel<128,64,64,32,3,128,true', (), 3, 64, 96, 8, 8, 0, taps=1),
-    # conv_lds_tables() is a statement about the automatic pick (tile 0), so the K = 32 and Winograd kernels are
+    # ConvChoice::lds_tables is a statement about the automatic pick (tile 0), so the K = 32 and Winograd kernels are
     # reached the way the plans reach them: a 64-pixel-wide map (2-D tiles), a split-K 4 x 4 map, Winograd weights
     _cv('k32_t2d_wide', 'conv_k32_kernel<128,128,64,64,true', (), 3, 64, 64, 8, 64, 0),
     _cv('k32s_4x4', 'conv_k32s_kernel<true', (), 3, 128, 64, 4, 4, 0, ksplit=2),
@@ -838,7 +838,7 @@ CONV_GIN_CASES = [
 CONV_GIN_REFUSED = [
     _cv('fp32_weights', '', (), 3, 64, 64, 8, 8, 4, split=False, refuse=True),
     _cv('bf16x3_weights', '', (), 3, 64, 64, 8, 8, 4, split='bf16x3', refuse=True),
-    _cv('forced_k32_tile', '', (), 3, 64, 64, 8, 8, 10, refuse=True),   # (conv_lds_tables knows the patch tiles only)
+    _cv('forced_k32_tile', '', (), 3, 64, 64, 8, 8, 10, refuse=True),   # (lds_tables knows the patch tiles only)
 ]
 
 

@@ -198,7 +198,7 @@ def test_symmetric_wide_downsample_keeps_its_path(cuda):
     dmhip.launch_log(False)
     ys = [_run_conv(cuda, xd, wp, Cout, H // 2, W // 2, 9, 2, 0, split='fp16x2', tile=t) for t in (1, 2, 3)]
     assert not any(SEG_NOTE in ln for ln in log), log
-    # M = 512 rows, Cout = 64: conv_pick's im2col choice is the 64 x 64 tile (fewer than 512 blocks of the larger ones)
+    # M = 512 rows, Cout = 64: conv_choose's im2col choice is the 64 x 64 tile (fewer than 512 blocks of the larger ones)
     assert torch.equal(y0.cpu(), ys[2].cpu())
     ref = _nhwc(F.conv2d(x.double(), w.double(), stride=2, padding=1))
     for yy in [y0] + ys:

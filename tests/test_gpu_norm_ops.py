@@ -484,7 +484,7 @@ def check_conv_gin(be, s, mod, nosilu):
 
 
 def check_conv_gin_refused(be, s):
-    """e. Where conv_lds_tables() is false the hook returns DM_ERR_UNSUPPORTED and launches nothing."""
+    """e. Where ConvChoice::lds_tables is false the hook returns DM_ERR_UNSUPPORTED and launches nothing."""
     r = be.conv_gin(s, 0, 0)
     assert r['rc'] == nr.UNSUPPORTED and untouched(r['y_gin']) and not r['log'], (s['name'], r['rc'], r['log'])
 
